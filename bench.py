@@ -1,6 +1,9 @@
 """Benchmark of the hot path: reverse-diffusion docking sampler on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--split complexes|samples]
+  python bench.py --gpus N --steps K --warmup W [--split complexes|samples] [--dump-outputs DIR] [--full]
+  A plain run measures the headline only: set-up, W warm-up complexes, the K timed ones, the outputs (--dump-outputs: the final
+  poses of the last timed complex, DIR/final_poses.npy) and the result line, whose `ms_per_step` is the time of one timed complex.
+  --full adds the secondary legs and the CPU baseline described below.
   N > 1: run bare, this process starts the N ranks itself (`python -m torch.distributed.run --nproc-per-node N ...`, before any
   GPU call is made here) and exits with their status; launched under torch.distributed.run (RANK / WORLD_SIZE set, as the
   driver does) it is one of the ranks.  Fails loudly -- non-zero exit, no JSON line -- when fewer than N GPUs are visible or
@@ -27,14 +30,14 @@ folded-protein density (135 A^3 per residue) with the pocket at 0.7 of the surfa
 in production; only the DATA differ.  The measured edge counts and FLOPs per pose-step are printed in `roofline`.
 `--poses free --geometry loose` reproduces the round-1 workload.  tests/test_gpu_configs.py checks THIS workload against the oracle.
 
-Rank 0 prints the secondary legs as their own short JSON lines ({"leg": name, ...}, in the order they are measured, then
+Rank 0 prints, with --full, the secondary legs as their own short JSON lines ({"leg": name, ...}, in the order they are measured), then
 {"leg": "headline_detail", ...} with the full config text and the work behind `value`) and LAST the one parsed line of the contract,
-kept under ~1.8 KB: headline fields + `roofline` + `cpu_baseline` + a compact {leg: [value, fraction]} map.  `roofline` (dominant kernel = tp_conv,
+kept under ~1.8 KB: headline fields + `roofline` (+ with --full `cpu_baseline` + a compact {leg: [value, fraction]} map).  `roofline` (dominant kernel = tp_conv,
 fp32 MFMA bound, duration from HIP events on the launch stream; `achieved` / `frac` count the FLOPs the kernel EXECUTES -- the
 layer-0 receptor->receptor messages are computed once per complex and shared by its samples -- the reference formulation's
 un-shared count is printed beside it as `algorithmic_tflops` / `algorithmic_frac`) and `cpu_baseline` (the oracle's PyTorch-CPU
 restatement of the same path, timed on a bounded sample on rank 0 at N=1 only: two poses through ALL 20 steps, no extrapolation over
-steps).  Secondary legs of the default N=1 run (never part of `value`): `python_api` (the same workload through `sampling()` incl. noise
+steps).  Secondary legs of an N=1 --full run (never part of `value`): `python_api` (the same workload through `sampling()` incl. noise
 drawing, co-scheduling, confidence ranking and write-back; timed with the cyclic GC off and on), `c4_bf16` (BASELINE.json configs[3]: 64 x
 40 on the large-pocket complex, bf16 operands), `single_complex` (one complex per launch / one `sampling()` call per complex, as the
 reference's inference.py loop runs it), `complex_set` (configs[2]: a heterogeneous set through distributed.run_complex_set), `confidence`,
@@ -574,11 +577,14 @@ def measure(model, margs, dev, *, workload, samples, denoise_steps, dtype, geome
     pos0, noise = [], []
     idx = torch.as_tensor(mine, dtype=torch.long)
     cols = (idx[:, None] * R + torch.arange(R)[None, :]).reshape(-1)
+    # randomize_position only re-binds ligand.pos, so shallow copies of one collated complex give the same poses as a deep copy per
+    # sample at a fraction of the setup time
+    base = Batch.from_data_list([copy.deepcopy(cplx)])
     for k in range(n_runs):
         seed = 42 + (0 if by_samples else 1000 * rank) + k
         torch.manual_seed(seed)
         np.random.seed(seed)
-        dl = [Batch.from_data_list([copy.deepcopy(cplx)]) for _ in range(samples)]
+        dl = [base.shallow_copy() for _ in range(samples)]
         randomize_position(dl, False, False, margs.tr_sigma_max)             # prior centred on the receptor centroid (no pocket knowledge)
         p0 = torch.stack([d["ligand"].pos for d in dl])
         z_tr = torch.randn(denoise_steps, samples, 3)
@@ -658,9 +664,9 @@ def measure(model, margs, dev, *, workload, samples, denoise_steps, dtype, geome
     if by_samples:
         # one ranked gather per complex (inference.py:537-547 ranks the samples of a complex; without a confidence model here: by index)
         for k in range(warmup, n_runs):
-            gather_ranked(on_wire(pos0[k]), on_wire(-idx.float().to(dev)), world, rank, 0, ids=idx, rows=-(-samples // world))
+            final = gather_ranked(on_wire(pos0[k]), on_wire(-idx.float().to(dev)), world, rank, 0, ids=idx, rows=-(-samples // world))[0]
     else:
-        gather_poses(on_wire(pos0[n_runs - 1]), world, rank)
+        final = gather_poses(on_wire(pos0[n_runs - 1]), world, rank)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -763,7 +769,7 @@ def measure(model, margs, dev, *, workload, samples, denoise_steps, dtype, geome
     ctx = None
     if keep:
         ctx = dict(engines=engines, pos0=pos0, noise=noise, run=run, alt_k=alt_k, alt_init=alt_init, n_runs=n_runs, cosched=cosched,
-                   cplx=cplx, sched=sched, geometry=geometry)
+                   cplx=cplx, sched=sched, geometry=geometry, final=final)
     return out, ctx
 
 
@@ -825,15 +831,37 @@ def final_line(out, legs):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, final):
+    """--dump-outputs DIR: what the timed path hands its caller for the LAST timed step -- the final poses of the last complex
+    (gathered from every rank to rank 0) -- as DIR/final_poses.npy, float32 [poses, Nl, 3].  Beyond 64 MB a fixed, seeded sample of
+    pose rows is written instead, with their indices in DIR/final_poses_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    pos = torch.cat([t.cpu() for t in final]) if isinstance(final, (list, tuple)) else final.cpu()
+    pos = pos.to(torch.float32).numpy()
+    row_bytes = pos[0].nbytes + 8
+    if pos.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(pos.shape[0], (DUMP_LIMIT_BYTES - 4096) // row_bytes, replace=False))
+        np.save(os.path.join(d, "final_poses_rows.npy"), rows.astype(np.float64))
+        pos = pos[rows]
+    np.save(os.path.join(d, "final_poses.npy"), pos)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--legs", default="", help="diagnostic: comma-separated subset of the secondary legs to run (default: all)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the secondary legs (python_api, c4_bf16, complex_set, confidence, "
-                    "other operand modes, fine-tuning, CPU baseline): the command the rocprofv3 --pmc passes under profiles/ are taken over")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the secondary legs (python_api, c4_bf16, single_complex, "
+                    "complex_set, confidence, other operand modes, fine-tuning, cb_round) and the CPU baseline; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the final poses of the last timed step to DIR/final_poses.npy "
+                    "(float32; the inputs are fixed by the arguments, so two builds can be compared output for output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--legs", default="", help="diagnostic, with --full: comma-separated subset of the secondary legs to run (default: all)")
+    ap.add_argument("--headline-only", action="store_true", help="skip the secondary legs and the CPU baseline even with --full (a plain run "
+                    "never runs them): the command the rocprofv3 --pmc passes under profiles/ are taken over")
     ap.add_argument("--graph", type=int, default=1, help="1 (default): the whole step loop of a group of complexes is one hipGraph launch, the "
                     "tensor-product kernels timed by event-record nodes of the graph; 0: eager launches")
     ap.add_argument("--workload", default=HEADLINE[0], help="synthetic complex: c2_dockgen_median (headline) or c4_large_pocket")
@@ -862,6 +890,8 @@ def main():
         use_diag_library()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "RANK" not in os.environ:
         launch_ranks(a.gpus, sys.argv[1:])          # does not return
 
@@ -898,8 +928,10 @@ def main():
                        rank=rank, world=world, split=a.split, keep=True, mark=a.mark_timed_region)
     if rank == 0:
         headline = (a.workload, a.samples, a.denoise_steps, a.dtype, a.geometry, a.poses) == HEADLINE
-        extras = world == 1 and headline and not a.headline_only
+        extras = world == 1 and headline and a.full and not a.headline_only
         engines, pos0, run, alt_k, alt_init, n_runs = (ctx[k] for k in ("engines", "pos0", "run", "alt_k", "alt_init", "n_runs"))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, ctx["final"])      # before the legs below re-run the last complexes in other operand modes
 
         legs = {}
 

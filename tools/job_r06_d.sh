@@ -7,7 +7,7 @@ timeout 1200 python -m pytest tests/test_gpu_train_step.py tests/test_gpu_train_
 for mode in "0 96" "1 96" "1 48" "1 64" "1 160"; do
   set -- $mode
   echo "== CBD_TRAIN_TWO_STREAMS=$1 CBD_DW_MAX_CHUNKS=$2"
-  CBD_TRAIN_TWO_STREAMS=$1 CBD_DW_MAX_CHUNKS=$2 timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --legs finetune,finetune_b5 2> $OUT/bench_$1_$2.err | grep '"leg": "finetune' | python -c "
+  CBD_TRAIN_TWO_STREAMS=$1 CBD_DW_MAX_CHUNKS=$2 timeout 600 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --legs finetune,finetune_b5 2> $OUT/bench_$1_$2.err | grep '"leg": "finetune' | python -c "
 import sys, json
 for ln in sys.stdin:
     d = json.loads(ln)

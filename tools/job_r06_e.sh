@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r06_e
 mkdir -p $OUT
-timeout 1800 python bench.py --steps 20 --warmup 5 > $OUT/bench_lines.json 2> $OUT/bench.err; tail -c 1700 $OUT/bench_lines.json
+timeout 1800 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_lines.json 2> $OUT/bench.err; tail -c 1700 $OUT/bench_lines.json
 python tools/engine_memory.py > $OUT/engine_memory.json 2>&1; cat $OUT/engine_memory.json
 python tools/engine_memory.py --workload c4_large_pocket --batch 64 > $OUT/engine_memory_c4.json 2>&1; cat $OUT/engine_memory_c4.json
 timeout 900 python -m pytest tests/test_gpu_bench_ranks.py tests/test_gpu_distributed.py tests/test_gpu_train_step.py tests/test_gpu_train_graph.py -q -s > $OUT/pytest_ranks.log 2>&1; grep -E "two ranks|passed|failed" $OUT/pytest_ranks.log

@@ -9,4 +9,4 @@ timeout 900 python -m pytest tests/test_gpu_bf16.py tests/test_gpu_configs.py te
 timeout 900 python tools/bf16_repeat.py 6 bf16 2>&1 | tail -1 | tee $OUT/bf16_repeat.txt
 bash tools/profile_c4_bf16.sh $TAG > $OUT/profile_c4.log 2>&1
 bash tools/pmc_c4_bf16.sh $TAG 2 > $OUT/pmc_c4.log 2>&1; tail -2 $OUT/pmc_bf16_summary.log | cut -c1-600
-timeout 1800 python bench.py --steps 20 --warmup 5 > $OUT/bench_lines.json 2> $OUT/bench.err; tail -c 1700 $OUT/bench_lines.json
+timeout 1800 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_lines.json 2> $OUT/bench.err; tail -c 1700 $OUT/bench_lines.json
