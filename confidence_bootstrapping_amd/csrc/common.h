@@ -107,6 +107,12 @@ struct ConvGroup {
 // of ConvGroup so that 32 of them fit the 4 KB kernel-argument limit.
 struct ConvGroupH : ConvGroup {
   int src_lo = 0, src_n = 0, dst_lo = 0, dst_n = 0;
+  // node-major 0e path (tp_node0e.hip): CSR ranges of the aggregating nodes (group-local index) and the group's buffers
+  const int* n0_start = nullptr;
+  const int* n0_cnt = nullptr;
+  int n0_nodes = 0;
+  float* n0_abuf = nullptr;
+  float* n0_out = nullptr;
 };
 
 // Up to 32 groups per launch: the 4 edge groups of one batch, or of up to EIGHT batches (engines working on different
@@ -126,6 +132,29 @@ struct ConvArgs {
 };
 static_assert(sizeof(ConvArgs) <= 4096, "ConvArgs is passed by value: HIP kernel arguments are limited to 4 KB");
 
+// Block 0e of the 74 -> 74 fp32 layers aggregated per node before the second Linear (tp_node0e.hip): one group's aggregating nodes.
+// abuf row of a node: A[k][j] for the 38 mids j in the B-operand order of the second Linear (96 floats per mid), then S[38].
+constexpr int N0E_S_OFF = (NS + NV) * 96;
+constexpr int N0E_ROW = N0E_S_OFF + 64;
+struct N0eGroup {
+  const int* start;      // [n_nodes] first edge of the node in the group's (src-sorted) edge list
+  const int* cnt;        // [n_nodes] its number of edges
+  const int *src, *dst, *attr_idx;
+  const float* vec;
+  const float* attr;
+  const float* wstream;  // the group's OpsF32 stream (conv_shape(3, 3, true))
+  const float* node_in;
+  const float *psrc, *pdst;
+  float* abuf;           // [n_nodes][N0E_ROW]
+  float* out;            // [n_nodes][NS]
+  int n_nodes;
+};
+struct N0eArgs {
+  N0eGroup g[CONV_MAX_GROUPS];
+  int n_groups;
+};
+static_assert(sizeof(N0eArgs) <= 4096, "N0eArgs is passed by value");
+
 // One edge group as seen by the finalize kernel: CSR range of every node + the partial sums written by tp_conv.
 struct FinGroup {
   const int* start;        // [nodes of this type] first edge of the node in the group's edge list
@@ -137,6 +166,7 @@ struct FinGroup {
   int node_mod;            // > 0: the group is shared by all samples, node k = i % node_mod (layer-0 receptor edges)
   int deg_weight;          // 1: its edges count towards the node's in-degree; 0: a further slice of an already counted group
   int col_hi;              // > 0: this slice's pieces hold only the columns [0, col_hi) (a 0e-only slice of the bf16 role split)
+  const float* node0e;     // [nodes of this type][NS] complete 0e sums of the node-major path (tp_node0e.hip), added when a layer ran it
 };
 struct FinArgs {
   FinGroup g[4];

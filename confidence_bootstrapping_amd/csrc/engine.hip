@@ -104,6 +104,10 @@ struct cbd_engine {
   float *fsum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *lsum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float* racc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float *fsum_x[2] = {nullptr, nullptr}, *lsum_x[2] = {nullptr, nullptr}, *racc_x[2] = {nullptr, nullptr};   // extra slices of ll (embedding layers)
+  // node-major 0e path of the 74 -> 74 fp32 layers (tp_node0e.hip), per group ll, lr, rr (also the shared layer-0 group), rl:
+  // A/S rows and the finished 0e sums of every aggregating node.  node0e = 0 ("node0e" option): the whole chain in the edge kernel.
+  float *n0_abuf[4] = {nullptr, nullptr, nullptr, nullptr}, *n0_out[4] = {nullptr, nullptr, nullptr, nullptr};
+  int node0e = 1;
   // bf16 role split ("bf16_roles" option): the cross / receptor groups (1 lr, 2 rr, 3 rl) run as three virtual slices per layer --
   // 0e tiles [0, 19), 0e tiles [19, 38), vector blocks; the second 0e slice writes piece buffers of its own, laid out exactly like
   // the group's and `piece_b_off[g]` floats behind them (first_sum, last_sum and run_acc alike)
@@ -711,7 +715,8 @@ static int record_event(hipEvent_t ev, hipStream_t s, bool capturing) {
   return 0;
 }
 
-static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArgs& a, int grid, hipStream_t s, const ConvArgs* resident = nullptr) {
+static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArgs& a, int grid, hipStream_t s, const ConvArgs* resident = nullptr,
+                             const N0eArgs* n0 = nullptr) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   bool cap = false;
   if (e->timing) {
@@ -733,6 +738,7 @@ static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArg
   else if (e->use_bf16 == 1) HIPCHK(launch_tp_conv_bf16(L.in_level, L.out_level, a, grid, s));
   else if (e->use_bf16 == 2) HIPCHK(launch_tp_conv_x3(L.in_level, L.out_level, a, grid, s));
   else HIPCHK(launch_tp_conv(L.in_level, L.out_level, a, grid, s));
+  if (n0) HIPCHK(launch_node0e(*n0, s));   // inside the timing events: tp_conv_ms still times the whole layer
 #ifdef CBD_EXPERIMENTS
   if (resident) HIPCHK(launch_tp_conv_bf16p(*resident, e->n_cus, s));
 #else
@@ -755,8 +761,14 @@ struct ConvJob {
 // One tensor-product launch (+ the node-projection launch in front of it) over the groups of all jobs: the batches of up to eight
 // complexes share every launch of the step loop, so a launch carries several times the waves of a single 40-pose batch (the
 // per-launch drain of the long-lived waves is amortised).  Timed by jobs[0].e.
-static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipStream_t s, bool side) {
+// use0e (layer_uses_node0e): block 0e of every group runs node-major (tp_node0e.hip) and the edge kernel runs the vector blocks only.
+static bool layer_uses_node0e(const cbd_engine* e, const ConvLayerDev& L) {
+  return e->node0e && e->use_bf16 == 0 && L.in_level == 3 && L.out_level == 3;
+}
+
+static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipStream_t s, bool side, bool use0e = false) {
   cbd_engine* e0 = jobs[0].e;
+  N0eArgs n0{};
   constexpr int MAX_ALL = 8 * 10;      // up to eight co-scheduled batches of ten slices
   static thread_local ConvGroup all[MAX_ALL];
   int caps[MAX_ALL];
@@ -779,6 +791,15 @@ static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipS
       if (G.i0e_hi == 0 && G.vec_on == 0) {   // not a virtual slice: the whole weight-tile chain
         G.i0e_lo = 0; G.i0e_hi = S.t0e; G.vec_on = 1;
       }
+      if (use0e) {
+        const ConvGroupH& H = J.g[g];
+        if (!H.n0_start || n0.n_groups == CONV_MAX_GROUPS || G.i0e_lo != 0 || G.i0e_hi != S.t0e || G.vec_on != 1)
+          return fail(CBD_ERR_STATE, "node-major 0e path: group without node ranges");
+        G.i0e_lo = G.i0e_hi = S.t0e;           // the edge kernel keeps the vector blocks
+        N0eGroup& N = n0.g[n0.n_groups++];
+        N.start = H.n0_start; N.cnt = H.n0_cnt; N.n_nodes = H.n0_nodes; N.abuf = H.n0_abuf; N.out = H.n0_out;
+        N.src = G.src; N.dst = G.dst; N.attr_idx = G.attr_idx; N.vec = G.vec; N.attr = G.attr; N.wstream = G.wstream; N.node_in = G.node_in;
+      }
       if (e0->use_bf16 != 1) {
         // per-node projections of the first Linear's node parts, one job per distinct (FCBlock, role); virtual slices share them.
         // (The plain-bf16 policy keeps the whole first Linear in the edge kernel.)
@@ -794,6 +815,7 @@ static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipS
         G.psrc = e->proj[base + 2 * slot_of[w]];
         G.pdst = e->proj[base + 2 * slot_of[w] + 1];
       }
+      if (use0e) { n0.g[n0.n_groups - 1].psrc = G.psrc; n0.g[n0.n_groups - 1].pdst = G.pdst; }
     }
   }
   if (pa.n_jobs) HIPCHK(launch_node_proj(pa, s));
@@ -813,7 +835,7 @@ static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipS
     if (!to_resident) grid += (caps[i] + edges_per_wg - 1) / edges_per_wg;
   }
   if (ap.n_groups) { ap.stamps = a.stamps; a.stamps = nullptr; }      // diagnostic stamps: the persistent kernel's
-  return launch_conv_timed(e0, L, a, grid, s, ap.n_groups ? &ap : nullptr);
+  return launch_conv_timed(e0, L, a, grid, s, ap.n_groups ? &ap : nullptr, use0e ? &n0 : nullptr);
 }
 
 static FinGroup fin_group(const ConvGroup& g, const int* start, const int* cnt, int node_mod = 0) {
@@ -1047,6 +1069,11 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
       HIPCHK(e->bpool.alloc(&e->lsum[g], sf));
       HIPCHK(e->bpool.alloc(&e->racc[g], sr));
     }
+    for (int g = 0; g < 4; ++g) {
+      const size_t nodes = (size_t)Bm * (g == 0 || g == 1 ? Nl : Nr);
+      HIPCHK(e->bpool.alloc(&e->n0_abuf[g], nodes * N0E_ROW));
+      HIPCHK(e->bpool.alloc(&e->n0_out[g], nodes * NS));
+    }
     for (int k = 0; k < 2; ++k) {
       const size_t tiles = (cap_ll + CONV_WG_EDGES - 1) / CONV_WG_EDGES + 1;
       HIPCHK(e->bpool.alloc(&e->fsum_x[k], tiles * NODE_STRIDE));
@@ -1112,6 +1139,9 @@ static BatchGroups batch_groups(cbd_engine* e, int B) {
   G.rl.src = gd.rl_src; G.rl.dst = gd.rl_dst; G.rl.attr_idx = gd.rl_aidx; G.rl.vec = gd.rl_vec; G.rl.attr = e->lr_attr; G.rl.count = gd.counts + 3;
   ConvGroupH* gg[4] = {&G.ll, &G.lr, &G.rr, &G.rl};
   for (int g = 0; g < 4; ++g) { gg[g]->first_sum = e->fsum[g]; gg[g]->last_sum = e->lsum[g]; gg[g]->run_acc = e->racc[g]; }
+  for (int g = 0; g < 4; ++g) { gg[g]->n0_abuf = e->n0_abuf[g]; gg[g]->n0_out = e->n0_out[g]; gg[g]->n0_nodes = g < 2 ? nL : nR; }
+  G.ll.n0_start = gd.start_ll; G.ll.n0_cnt = gd.cnt_ll; G.lr.n0_start = gd.start_lr; G.lr.n0_cnt = gd.cnt_lr;
+  G.rr.n0_start = e->rr_start; G.rr.n0_cnt = e->rr_cnt; G.rl.n0_start = gd.start_rl; G.rl.n0_cnt = gd.cnt_rl;
   // node-row ranges of the aggregating (src) and the read (dst) side: ligand rows [0, nL), receptor rows [rec_off, rec_off + nR)
   G.ll.src_lo = 0; G.ll.src_n = nL; G.ll.dst_lo = 0; G.ll.dst_n = nL;
   G.lr.src_lo = 0; G.lr.src_n = nL; G.lr.dst_lo = gs.rec_off; G.lr.dst_n = nR;
@@ -1131,6 +1161,9 @@ static BatchGroups batch_groups(cbd_engine* e, int B) {
   G.rr_shared.attr = e->rr_attr_t; G.rr_shared.count = e->rr_count_dev;
   G.rr_shared.first_sum = e->fsum[4]; G.rr_shared.last_sum = e->lsum[4]; G.rr_shared.run_acc = e->racc[2];
   G.rr_shared.src_lo = gs.rec_off; G.rr_shared.src_n = gs.Nr; G.rr_shared.dst_lo = gs.rec_off; G.rr_shared.dst_n = gs.Nr;
+  // the first Nr CSR ranges of the batched receptor graph are sample 0's = the shared group's; rr itself does not run in layer 0
+  G.rr_shared.n0_start = e->rr_start; G.rr_shared.n0_cnt = e->rr_cnt; G.rr_shared.n0_nodes = gs.Nr;
+  G.rr_shared.n0_abuf = e->n0_abuf[2]; G.rr_shared.n0_out = e->n0_out[2];
   return G;
 }
 
@@ -1164,9 +1197,10 @@ static void fill_static_desc(cbd_engine* e) {
   D.stats = e->stats_dev;
   const BatchGroups G = batch_groups(e, e->cfg.max_batch);   // pointers only: independent of B
   const GraphDyn& gd = e->gd;
-  const FinGroup f_ll = fin_group(G.ll, gd.start_ll, gd.cnt_ll), f_lr = fin_group(G.lr, gd.start_lr, gd.cnt_lr);
-  const FinGroup f_rl = fin_group(G.rl, gd.start_rl, gd.cnt_rl), f_rr = fin_group(G.rr, e->rr_start, e->rr_cnt);
-  const FinGroup f_rr_shared = fin_group(G.rr_shared, e->rr_start, e->rr_cnt, e->gs.Nr);
+  FinGroup f_ll = fin_group(G.ll, gd.start_ll, gd.cnt_ll), f_lr = fin_group(G.lr, gd.start_lr, gd.cnt_lr);
+  FinGroup f_rl = fin_group(G.rl, gd.start_rl, gd.cnt_rl), f_rr = fin_group(G.rr, e->rr_start, e->rr_cnt);
+  FinGroup f_rr_shared = fin_group(G.rr_shared, e->rr_start, e->rr_cnt, e->gs.Nr);
+  f_ll.node0e = e->n0_out[0]; f_lr.node0e = e->n0_out[1]; f_rr.node0e = e->n0_out[2]; f_rl.node0e = e->n0_out[3]; f_rr_shared.node0e = e->n0_out[2];
   D.fin_lig.n_groups = 2; D.fin_lig.g[0] = f_ll; D.fin_lig.g[1] = f_lr;
   D.fin_rec.n_groups = 2; D.fin_rec.g[0] = f_rr; D.fin_rec.g[1] = f_rl;
   D.fin_rec_shared.n_groups = 2; D.fin_rec_shared.g[0] = f_rr_shared; D.fin_rec_shared.g[1] = f_rl;
@@ -1243,7 +1277,7 @@ static int forward_multi(cbd_engine* const* E, int n, const cbd_step& st, const 
       ConvJob& J = jobs[k];
       J.e = E[k]; J.n_groups = 1; J.g[0] = G[k].rr_shared; J.caps[0] = E[k]->gs.Err; J.widx[0] = 2; J.node_in = E[k]->X1;
     }
-    CHK(run_conv(e0->conv[0], jobs, n, ss, true));
+    CHK(run_conv(e0->conv[0], jobs, n, ss, true, layer_uses_node0e(e0, e0->conv[0])));
     HIPCHK(hipEventRecord(e0->ev_join, ss));
   }
   const float lig_r = e0->cfg.lig_max_radius;
@@ -1333,10 +1367,11 @@ static int forward_multi(cbd_engine* const* E, int n, const cbd_step& st, const 
         J.caps[0] = cap_ll; J.caps[1] = cap_x;
       }
     }
-    CHK(run_conv(L, jobs, n, s, false));
+    const bool use0e = !roles && layer_uses_node0e(e0, L);
+    CHK(run_conv(L, jobs, n, s, false, use0e));
     const int kind = (l == 0 ? FIN_FIRST : l < 4 ? FIN_MID : FIN_LAST) + (roles ? FIN_FIRST_R - FIN_FIRST : 0);   // receptor rows of the last layer are never read again (quirk 3)
     HIPCHK(launch_conv_finalize_multi(l < 4 ? m_all_nodes : m_lig_nodes, kind, xi, xi ^ 1, L.bn_scale, L.bn_mean, L.bn_bias,
-                                      in_level_dim(L.in_level), out_level_dim(L.out_level), s));
+                                      in_level_dim(L.in_level), out_level_dim(L.out_level), s, use0e ? 1 : 0));
     xi ^= 1;
     if (dbg) {
       snap(e0, conv_names[l], e0->desc_h.X[xi], (size_t)nl(0) * NODE_STRIDE, s);
@@ -1624,6 +1659,11 @@ int cbd_set_option(cbd_engine* e, const char* name, int64_t value) {
   }
   if (k == "bf16_stationary") {   // bf16 only: register-stationary kernel for the 74 -> 74 layers (captured graphs bake it in)
     e->bf16_stat = value != 0;
+    drop_graphs(e);
+    return 0;
+  }
+  if (k == "node0e") {   // fp32 74 -> 74 layers: block 0e aggregated per node before the second Linear (tp_node0e.hip; default 1)
+    e->node0e = value != 0;
     drop_graphs(e);
     return 0;
   }

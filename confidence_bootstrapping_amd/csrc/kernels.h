@@ -149,12 +149,15 @@ hipError_t launch_tp_conv_bf16p(const ConvArgs& a, int n_wg, hipStream_t s);
 // the 74 -> 74 layers of the bf16 policy with register-stationary weights: persistent workgroups of four waves, one per CU (tp_conv_bf16s.hip)
 hipError_t launch_tp_conv_bf16s(const ConvArgs& a, int n_wg, hipStream_t s);
 bool tp_conv_bf16s_fits(const ConvArgs& a);      // false: the launch does not fit that kernel (virtual slices, more FCBlocks than its role table holds) -> streaming kernel
+// tp_node0e.hip: block 0e of the 74 -> 74 fp32 layers per aggregating node (A/S build, then the second Linear with nodes on N)
+hipError_t launch_node0e(const N0eArgs& a, hipStream_t s);
 hipError_t launch_tp_conv_x3(int in_level, int out_level, const ConvArgs& a, int grid, hipStream_t s);     // bf16x3 weight streams
 // segmented sum -> mean -> BatchNorm -> residual of one layer for every batch.  kind: which node types / group sets take part
 enum FinKind { FIN_EMB = 0, FIN_FIRST = 1, FIN_MID = 2, FIN_LAST = 3,     // ligand embedding layer; interaction layer 0; 1..3; 4
                FIN_FIRST_R = 5, FIN_MID_R = 6, FIN_LAST_R = 7 };           // ... of the bf16 role split (fin_*_r group sets; diagnostic library only)
+// use0e: add FinGroup::node0e (the layer ran the node-major 0e path)
 hipError_t launch_conv_finalize_multi(const Multi& m, int kind, int xi_in, int xi_out, const float* bn_scale, const float* bn_mean,
-                                      const float* bn_bias, int in_dim, int out_dim, hipStream_t s);
+                                      const float* bn_bias, int in_dim, int out_dim, hipStream_t s, int use0e = 0);
 // single list of nodes with explicit groups (receptor embedding at set-up time)
 hipError_t launch_conv_finalize(const FinArgs& fa, const float* node_in, float* node_out, const float* bn_scale,
                                 const float* bn_mean, const float* bn_bias, int n_nodes, int in_dim, int out_dim,

@@ -366,7 +366,8 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
 // eps) per column; bn_mean / bn_bias are zero outside the 0e columns.
 __device__ __forceinline__ void finalize_one(const FinArgs& fa, const float* __restrict__ node_in, float* __restrict__ node_out,
                                              const float* __restrict__ bn_scale, const float* __restrict__ bn_mean,
-                                             const float* __restrict__ bn_bias, int i, int c, int in_dim, int out_dim, int node_off) {
+                                             const float* __restrict__ bn_bias, int i, int c, int in_dim, int out_dim, int node_off,
+                                             bool use0e = false) {
   const size_t o = (size_t)(i + node_off) * NODE_STRIDE + c;
   float r = 0.f;
   if (c < out_dim) {
@@ -388,6 +389,7 @@ __device__ __forceinline__ void finalize_one(const FinArgs& fa, const float* __r
         sum += (at_start ? G.first_sum : G.last_sum)[(size_t)t0 * NODE_STRIDE + c];
         for (int t = t0 + 1; t <= t1; ++t) sum += G.first_sum[(size_t)t * NODE_STRIDE + c];
       }
+      if (use0e && G.node0e && c < NS) sum += G.node0e[(size_t)k * NS + c];
     }
     float m = sum / (float)(deg > 1 ? deg : 1);
     m = (m - bn_mean[c]) * bn_scale[c] + bn_bias[c];
@@ -417,7 +419,8 @@ __device__ __forceinline__ const PoseBatch& fin_locate(const Multi& m, int& loca
 }
 
 __global__ void conv_finalize_multi_kernel(Multi mm, int kind, int xi_in, int xi_out, const float* __restrict__ bn_scale,
-                                           const float* __restrict__ bn_mean, const float* __restrict__ bn_bias, int in_dim, int out_dim) {
+                                           const float* __restrict__ bn_mean, const float* __restrict__ bn_bias, int in_dim, int out_dim,
+                                           int use0e) {
   int blk;
   const PoseBatch& PB = fin_locate(mm, blk);
   const int idx = blk * blockDim.x + threadIdx.x;
@@ -429,14 +432,16 @@ __global__ void conv_finalize_multi_kernel(Multi mm, int kind, int xi_in, int xi
   const float* node_in = PB.X[xi_in];
   float* node_out = PB.X[xi_out];
 #ifdef CBD_EXPERIMENTS
+  // (the role split belongs to the bf16 policy: the engine never runs the node-major 0e path with it, use0e is 0 there)
   if (i < n0) finalize_one(base == FIN_EMB ? PB.fin_emb : roles ? PB.fin_lig_r : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim,
-                           out_dim, 0);
+                           out_dim, 0, use0e != 0);
   else finalize_one(base == FIN_FIRST ? (roles ? PB.fin_rec_shared_r : PB.fin_rec_shared) : (roles ? PB.fin_rec_r : PB.fin_rec), node_in, node_out,
-                    bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim, PB.gs.rec_off);
+                    bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim, PB.gs.rec_off, use0e != 0);
 #else
-  if (i < n0) finalize_one(base == FIN_EMB ? PB.fin_emb : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim, out_dim, 0);
+  if (i < n0) finalize_one(base == FIN_EMB ? PB.fin_emb : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim, out_dim, 0,
+                           use0e != 0);
   else finalize_one(base == FIN_FIRST ? PB.fin_rec_shared : PB.fin_rec, node_in, node_out, bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim,
-                    PB.gs.rec_off);
+                    PB.gs.rec_off, use0e != 0);
 #endif
 }
 
@@ -661,10 +666,10 @@ hipError_t launch_conv_finalize(const FinArgs& fa, const float* node_in, float* 
 
 // m: ceil((n0 + n1) * NODE_STRIDE / 256) workgroups per batch with n0 = B * Nl and n1 = B * Nr for the kinds that include receptor rows
 hipError_t launch_conv_finalize_multi(const Multi& m, int kind, int xi_in, int xi_out, const float* bn_scale, const float* bn_mean,
-                                      const float* bn_bias, int in_dim, int out_dim, hipStream_t s) {
+                                      const float* bn_bias, int in_dim, int out_dim, hipStream_t s, int use0e) {
   if (m.off[m.n] <= 0) return hipSuccess;
   hipLaunchKernelGGL(conv_finalize_multi_kernel, dim3(m.off[m.n]), dim3(256), 0, s, m, kind, xi_in, xi_out, bn_scale, bn_mean, bn_bias,
-                     in_dim, out_dim);
+                     in_dim, out_dim, use0e);
   return hipGetLastError();
 }
 
