@@ -128,7 +128,7 @@ static_assert(sizeof(ProjArgs) <= 4096, "ProjArgs is passed by value");
 struct ConvArgs {
   ConvGroup g[CONV_MAX_GROUPS];
   int n_groups;
-  unsigned long long* stamps;   // diagnostic build only (CBD_CONV_VARIANT=8): [grid][4] s_memtime/s_memrealtime at start/end
+  unsigned long long* stamps;   // diagnostic library only (CBD_CONV_VARIANT=8, CBD_BF16_DIAG=4..6; null otherwise): [grid][4] s_memtime/s_memrealtime at start/end
 };
 static_assert(sizeof(ConvArgs) <= 4096, "ConvArgs is passed by value: HIP kernel arguments are limited to 4 KB");
 
@@ -165,7 +165,7 @@ struct FinGroup {
   const float* run_acc;
   int node_mod;            // > 0: the group is shared by all samples, node k = i % node_mod (layer-0 receptor edges)
   int deg_weight;          // 1: its edges count towards the node's in-degree; 0: a further slice of an already counted group
-  int col_hi;              // > 0: this slice's pieces hold only the columns [0, col_hi) (a 0e-only slice of the bf16 role split)
+  int col_hi;              // > 0: this slice's pieces hold only the columns [0, col_hi) (a 0e-only slice of an embedding layer)
   const float* node0e;     // [nodes of this type][NS] complete 0e sums of the node-major path (tp_node0e.hip), added when a layer ran it
 };
 struct FinArgs {

@@ -108,20 +108,9 @@ struct cbd_engine {
   // A/S rows and the finished 0e sums of every aggregating node.  node0e = 0 ("node0e" option): the whole chain in the edge kernel.
   float *n0_abuf[4] = {nullptr, nullptr, nullptr, nullptr}, *n0_out[4] = {nullptr, nullptr, nullptr, nullptr};
   int node0e = 1;
-  // bf16 role split ("bf16_roles" option): the cross / receptor groups (1 lr, 2 rr, 3 rl) run as three virtual slices per layer --
-  // 0e tiles [0, 19), 0e tiles [19, 38), vector blocks; the second 0e slice writes piece buffers of its own, laid out exactly like
-  // the group's and `piece_b_off[g]` floats behind them (first_sum, last_sum and run_acc alike)
-  // EXPERIMENT (lost: 217 -> 163 poses/s): compiled only into the diagnostic library (-DCBD_EXPERIMENTS,
-  // tools/diag_lib.py, experiments/csrc/tp_conv_bf16p.hip); in the product library `bf16_roles` is the constant 0 and the option is refused
-#ifdef CBD_EXPERIMENTS
-  long long piece_b_off[4] = {0, 0, 0, 0};
-  int bf16_roles = 0;      // 1: the slices run through the streaming kernel, 2: the 0e slices through the LDS-resident kernel (tp_conv_bf16p.hip)
-#else
-  static constexpr int bf16_roles = 0;
-#endif
   // 1: the 74 -> 74 layers of the bf16 policy run through the register-stationary kernel (tp_conv_bf16s.hip; "bf16_stationary" option / CBD_BF16_STATIONARY;
   // the default since the end of round 5: 2 .. 4 % faster than the streaming kernel on C2 and C4, profiles/r05_c_*); 0: through the streaming
-  // kernel.  Ignored under the role split.
+  // kernel.
   int bf16_stat = 1;
   int n_cus = 256;
   int *rr_start = nullptr, *rr_cnt = nullptr;   // [max_batch*Nr] CSR ranges of the batched receptor edges
@@ -512,14 +501,8 @@ int cbd_create(const cbd_config* cfg, cbd_engine** out) {
   cbd_engine* e = new cbd_engine();
   e->cfg = *cfg;
   if (const char* p = getenv("CBD_PRECISION")) e->use_bf16 = std::max(0, std::min(2, atoi(p)));   // test hook: default operand policy
-#ifdef CBD_EXPERIMENTS
-  if (const char* p = getenv("CBD_BF16_ROLES")) e->bf16_roles = std::max(0, std::min(2, atoi(p)));                     // test hook: role split of the bf16 policy
-#endif
   if (const char* p = getenv("CBD_BF16_STATIONARY")) e->bf16_stat = atoi(p) != 0;                                       // test hook: register-stationary bf16 kernel
   HIPCHK(hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
-#ifdef CBD_EXPERIMENTS
-  if (const char* p = getenv("CBD_BF16P_WGS")) e->n_cus = std::max(1, atoi(p));                   // diagnostic: workgroups of the persistent kernel
-#endif
   HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
   HIPCHK(hipEventCreateWithFlags(&e->ev_last, hipEventDisableTiming));
@@ -715,8 +698,7 @@ static int record_event(hipEvent_t ev, hipStream_t s, bool capturing) {
   return 0;
 }
 
-static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArgs& a, int grid, hipStream_t s, const ConvArgs* resident = nullptr,
-                             const N0eArgs* n0 = nullptr) {
+static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArgs& a, int grid, hipStream_t s, const N0eArgs* n0 = nullptr) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   bool cap = false;
   if (e->timing) {
@@ -734,16 +716,11 @@ static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArg
     ++used;
     CHK(record_event(e0, s, cap));
   }
-  if (e->use_bf16 == 1 && e->bf16_stat && e->bf16_roles == 0 && L.in_level == 3 && L.out_level == 3 && tp_conv_bf16s_fits(a)) HIPCHK(launch_tp_conv_bf16s(a, e->n_cus, s));
+  if (e->use_bf16 == 1 && e->bf16_stat && L.in_level == 3 && L.out_level == 3 && tp_conv_bf16s_fits(a)) HIPCHK(launch_tp_conv_bf16s(a, e->n_cus, s));
   else if (e->use_bf16 == 1) HIPCHK(launch_tp_conv_bf16(L.in_level, L.out_level, a, grid, s));
   else if (e->use_bf16 == 2) HIPCHK(launch_tp_conv_x3(L.in_level, L.out_level, a, grid, s));
   else HIPCHK(launch_tp_conv(L.in_level, L.out_level, a, grid, s));
   if (n0) HIPCHK(launch_node0e(*n0, s));   // inside the timing events: tp_conv_ms still times the whole layer
-#ifdef CBD_EXPERIMENTS
-  if (resident) HIPCHK(launch_tp_conv_bf16p(*resident, e->n_cus, s));
-#else
-  (void)resident;
-#endif
   if (e->timing) CHK(record_event(e1, s, cap));
   return 0;
 }
@@ -751,9 +728,9 @@ static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArg
 // The edge groups ONE pose batch contributes to a tensor-product launch.
 struct ConvJob {
   cbd_engine* e = nullptr;
-  ConvGroupH g[10];                // 4 edge groups, or ll + three slices of each of the other three (bf16 role split)
-  int caps[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int widx[10] = {0, 1, 2, 3, 0, 0, 0, 0, 0, 0};      // which FCBlock of the layer each group uses
+  ConvGroupH g[4];                 // the edge groups ll, lr, rr, rl of an interaction layer, or the slices of ll (embedding layers)
+  int caps[4] = {0, 0, 0, 0};
+  int widx[4] = {0, 1, 2, 3};      // which FCBlock of the layer each group uses
   int n_groups = 0;
   const float* node_in = nullptr;
 };
@@ -769,7 +746,7 @@ static bool layer_uses_node0e(const cbd_engine* e, const ConvLayerDev& L) {
 static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipStream_t s, bool side, bool use0e = false) {
   cbd_engine* e0 = jobs[0].e;
   N0eArgs n0{};
-  constexpr int MAX_ALL = 8 * 10;      // up to eight co-scheduled batches of ten slices
+  constexpr int MAX_ALL = MAX_COSCHED * 4;      // up to eight co-scheduled batches of four groups
   static thread_local ConvGroup all[MAX_ALL];
   int caps[MAX_ALL];
   int n_all = 0;
@@ -819,23 +796,16 @@ static int run_conv(const ConvLayerDev& L, const ConvJob* jobs, int n_jobs, hipS
     }
   }
   if (pa.n_jobs) HIPCHK(launch_node_proj(pa, s));
-  // role split with resident weights (bf16_roles == 2): the 0e-only slices go to the persistent kernel (tp_conv_bf16p.hip), everything
-  // else stays with the streaming one
-  const bool resident = e0->use_bf16 == 1 && e0->bf16_roles == 2 && L.in_level == 3 && L.out_level == 3;
   const int edges_per_wg = e0->use_bf16 == 1 ? 64 : CONV_WG_EDGES;                    // bf16: one wave per 64 edges
-  ConvArgs a{}, ap{};
+  ConvArgs a{};
   a.stamps = e0->stamps_dev;
   int grid = 0;
   for (int i = 0; i < n_all; ++i) {
-    const ConvGroup& G = all[i];
-    const bool to_resident = resident && G.vec_on == 0 && G.i0e_hi > G.i0e_lo;
-    ConvArgs& t = to_resident ? ap : a;
-    if (t.n_groups == CONV_MAX_GROUPS) return fail(CBD_ERR_STATE, "too many edge groups in one launch");
-    t.g[t.n_groups++] = G;
-    if (!to_resident) grid += (caps[i] + edges_per_wg - 1) / edges_per_wg;
+    if (a.n_groups == CONV_MAX_GROUPS) return fail(CBD_ERR_STATE, "too many edge groups in one launch");
+    a.g[a.n_groups++] = all[i];
+    grid += (caps[i] + edges_per_wg - 1) / edges_per_wg;
   }
-  if (ap.n_groups) { ap.stamps = a.stamps; a.stamps = nullptr; }      // diagnostic stamps: the persistent kernel's
-  return launch_conv_timed(e0, L, a, grid, s, ap.n_groups ? &ap : nullptr, use0e ? &n0 : nullptr);
+  return launch_conv_timed(e0, L, a, grid, s, use0e ? &n0 : nullptr);
 }
 
 static FinGroup fin_group(const ConvGroup& g, const int* start, const int* cnt, int node_mod = 0) {
@@ -1055,16 +1025,6 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
     for (int g = 0; g < 5; ++g) {
       const size_t tiles = (caps[g] + CONV_WG_EDGES - 1) / CONV_WG_EDGES + 1;
       const size_t sf = tiles * NODE_STRIDE, sr = (size_t)(g == 4 ? Nr : N) * NODE_STRIDE;
-#ifdef CBD_EXPERIMENTS
-      if (g >= 1 && g <= 3) {   // one block: [first | last | run_acc] of the group, then the same again for its second 0e slice
-        const size_t D = (2 * sf + sr + 63) / 64 * 64;
-        float* base = nullptr;
-        HIPCHK(e->bpool.alloc(&base, 2 * D));
-        e->fsum[g] = base; e->lsum[g] = base + sf; e->racc[g] = base + 2 * sf;
-        e->piece_b_off[g] = (long long)D;
-        continue;
-      }
-#endif
       HIPCHK(e->bpool.alloc(&e->fsum[g], sf));
       HIPCHK(e->bpool.alloc(&e->lsum[g], sf));
       HIPCHK(e->bpool.alloc(&e->racc[g], sr));
@@ -1095,7 +1055,7 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
   HIPCHK(e->bpool.alloc(&e->stats_dev, 4));
   e->stamps_dev = nullptr;
 #ifdef CBD_DIAG      // the stamping kernels exist in the diagnostic library only
-  if ((getenv("CBD_CONV_VARIANT") && (atoi(getenv("CBD_CONV_VARIANT")) == 8 || atoi(getenv("CBD_CONV_VARIANT")) == 13)) ||
+  if ((getenv("CBD_CONV_VARIANT") && atoi(getenv("CBD_CONV_VARIANT")) == 8) ||
       (getenv("CBD_BF16_DIAG") && (atoi(getenv("CBD_BF16_DIAG")) >= 4 && atoi(getenv("CBD_BF16_DIAG")) <= 6))) {
     HIPCHK(e->bpool.alloc(&e->stamps_dev, 8192 * 8));
     HIPCHK(hipMemsetAsync(e->stamps_dev, 0, 8192 * 8 * 8, s));
@@ -1170,6 +1130,7 @@ static BatchGroups batch_groups(cbd_engine* e, int B) {
 // The ligand embedding layers hold only ~10 edge tiles per pose (a fraction of one round of waves) and are bound by the length of a
 // wave's weight-tile chain: the chain is split over two waves per edge tile (virtual slices of the ll group with their own pieces).
 constexpr int EMB_SLICES = 2;
+static_assert(EMB_SLICES <= 4, "ConvJob holds four groups");
 static void emb_slices(cbd_engine* e, const ConvGroupH& gll, int level, ConvGroupH (&sl)[EMB_SLICES]) {
   const ConvShape ES = conv_shape(level, level + 1);
   const int tvec = ES.t1o + ES.t1e + ES.t0o, nsl = EMB_SLICES;
@@ -1204,19 +1165,6 @@ static void fill_static_desc(cbd_engine* e) {
   D.fin_lig.n_groups = 2; D.fin_lig.g[0] = f_ll; D.fin_lig.g[1] = f_lr;
   D.fin_rec.n_groups = 2; D.fin_rec.g[0] = f_rr; D.fin_rec.g[1] = f_rl;
   D.fin_rec_shared.n_groups = 2; D.fin_rec_shared.g[0] = f_rr_shared; D.fin_rec_shared.g[1] = f_rl;
-#ifdef CBD_EXPERIMENTS
-  {   // bf16 role split: + the second 0e slice (columns [0, NS) only, not counted in the degree) of every cross / receptor group
-    auto second = [&](const FinGroup& f, int g) {
-      FinGroup b = f;
-      b.first_sum = f.first_sum + e->piece_b_off[g]; b.last_sum = f.last_sum + e->piece_b_off[g]; b.run_acc = f.run_acc + e->piece_b_off[g];
-      b.deg_weight = 0; b.col_hi = NS;
-      return b;
-    };
-    D.fin_lig_r.n_groups = 3; D.fin_lig_r.g[0] = f_ll; D.fin_lig_r.g[1] = f_lr; D.fin_lig_r.g[2] = second(f_lr, 1);
-    D.fin_rec_r.n_groups = 4; D.fin_rec_r.g[0] = f_rr; D.fin_rec_r.g[1] = f_rl; D.fin_rec_r.g[2] = second(f_rr, 2); D.fin_rec_r.g[3] = second(f_rl, 3);
-    D.fin_rec_shared_r.n_groups = 3; D.fin_rec_shared_r.g[0] = f_rr_shared; D.fin_rec_shared_r.g[1] = f_rl; D.fin_rec_shared_r.g[2] = second(f_rl, 3);
-  }
-#endif
   ConvGroupH sl[EMB_SLICES];
   emb_slices(e, G.ll, 0, sl);   // the piece buffers of the slices do not depend on the layer
   D.fin_emb.n_groups = EMB_SLICES;
@@ -1322,7 +1270,6 @@ static int forward_multi(cbd_engine* const* E, int n, const cbd_step& st, const 
   // ---- join: X[xi] (== X1) now holds the embedded ligand rows (main stream) and the receptor rows (side stream)
   HIPCHK(hipStreamWaitEvent(s, e0->ev_join, 0));
   static const char* conv_names[5] = {"conv_0", "conv_1", "conv_2", "conv_3", "conv_4"};
-  const bool roles = e0->use_bf16 == 1 && e0->bf16_roles != 0;
   for (int l = 0; l < 5; ++l) {   // interaction layers on the joint graph (score_model.py:365-374)
     const ConvLayerDev& L = e0->conv[l];
     for (int k = 0; k < n; ++k) {
@@ -1330,28 +1277,6 @@ static int forward_multi(cbd_engine* const* E, int n, const cbd_step& st, const 
       J = ConvJob{};
       J.e = E[k]; J.node_in = E[k]->desc_h.X[xi];
       const int cap_ll = E[k]->desc_h.cap_ll, cap_x = E[k]->desc_h.cap_x, cap_rr = Bk[k] * E[k]->gs.Err;
-#ifdef CBD_EXPERIMENTS
-      if (roles) {
-        // three virtual slices per cross / receptor group: 0e tiles [0, h0), [h0, t0e) and the vector blocks; what each costs a CU is
-        // a third of the weight stream, and the persistent kernel keeps a 0e slice's tiles in LDS (tp_conv_bf16p.hip)
-        const ConvShape S3 = conv_shape(3, 3);
-        const int h0 = (S3.t0e + 1) / 2;
-        J.n_groups = 0;
-        auto add = [&](const ConvGroupH& g, int cap, int w) { J.g[J.n_groups] = g; J.caps[J.n_groups] = cap; J.widx[J.n_groups] = w; ++J.n_groups; };
-        auto add3 = [&](const ConvGroupH& g, int gi, int cap, int w) {
-          ConvGroupH a = g, b = g, c = g;
-          a.i0e_lo = 0; a.i0e_hi = h0; a.vec_on = 0;
-          b.i0e_lo = h0; b.i0e_hi = S3.t0e; b.vec_on = 0;
-          b.first_sum += E[k]->piece_b_off[gi]; b.last_sum += E[k]->piece_b_off[gi]; b.run_acc += E[k]->piece_b_off[gi];
-          c.i0e_lo = S3.t0e; c.i0e_hi = S3.t0e; c.vec_on = 1;
-          add(a, cap, w); add(b, cap, w); add(c, cap, w);
-        };
-        add(G[k].ll, cap_ll, 0);
-        add3(G[k].lr, 1, cap_x, 1);
-        if (l >= 1 && l < 4) add3(G[k].rr, 2, cap_rr, 2);
-        if (l < 4) add3(G[k].rl, 3, cap_x, 3);
-      } else
-#endif
       if (l == 0) {          // the receptor->receptor group of layer 0 is the shared one computed on the side stream
         J.n_groups = 3;
         J.g[0] = G[k].ll; J.g[1] = G[k].lr; J.g[2] = G[k].rl;
@@ -1367,9 +1292,9 @@ static int forward_multi(cbd_engine* const* E, int n, const cbd_step& st, const 
         J.caps[0] = cap_ll; J.caps[1] = cap_x;
       }
     }
-    const bool use0e = !roles && layer_uses_node0e(e0, L);
+    const bool use0e = layer_uses_node0e(e0, L);
     CHK(run_conv(L, jobs, n, s, false, use0e));
-    const int kind = (l == 0 ? FIN_FIRST : l < 4 ? FIN_MID : FIN_LAST) + (roles ? FIN_FIRST_R - FIN_FIRST : 0);   // receptor rows of the last layer are never read again (quirk 3)
+    const int kind = l == 0 ? FIN_FIRST : l < 4 ? FIN_MID : FIN_LAST;   // receptor rows of the last layer are never read again (quirk 3)
     HIPCHK(launch_conv_finalize_multi(l < 4 ? m_all_nodes : m_lig_nodes, kind, xi, xi ^ 1, L.bn_scale, L.bn_mean, L.bn_bias,
                                       in_level_dim(L.in_level), out_level_dim(L.out_level), s, use0e ? 1 : 0));
     xi ^= 1;
@@ -1527,7 +1452,7 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
       e->complex_gen = cbd_engine::next_gen();
     }
     char buf[96];
-    snprintf(buf, sizeof buf, "|%p:%llu:%d:%d:%d:%d", (void*)e, (unsigned long long)e->complex_gen, (int)B[k], e->use_bf16 + 8 * e->bf16_roles + 32 * e->bf16_stat,
+    snprintf(buf, sizeof buf, "|%p:%llu:%d:%d:%d:%d", (void*)e, (unsigned long long)e->complex_gen, (int)B[k], e->use_bf16 + 32 * e->bf16_stat,
              (nz(noise_tr, k) != nullptr) + 2 * (nz(noise_rot, k) != nullptr) + 4 * (nz(noise_tor, k) != nullptr), (int)e->timing);
     key += buf;
   }
@@ -1605,7 +1530,7 @@ int cbd_sample_multi(int32_t n, cbd_engine* const* engines, const int32_t* B, in
       if (engines[q] == e) return fail(CBD_ERR_ARG, "distinct engines are required");
     if (!pos_dev[k]) return fail(CBD_ERR_ARG, "null pose buffer");
     if (e->cfg.device != e0->cfg.device) return fail(CBD_ERR_ARG, "co-scheduled engines must live on the same device");
-    if (e->use_bf16 != e0->use_bf16 || int(e->bf16_roles) - int(e0->bf16_roles) != 0 || e->bf16_stat != e0->bf16_stat) return fail(CBD_ERR_ARG, "co-scheduled engines must use the same operand precision");
+    if (e->use_bf16 != e0->use_bf16 || e->bf16_stat != e0->bf16_stat) return fail(CBD_ERR_ARG, "co-scheduled engines must use the same operand precision");
     if (e->cfg.no_torsion != e0->cfg.no_torsion || e->cfg.lig_max_radius != e0->cfg.lig_max_radius ||
         e->cfg.lig_radius_cap != e0->cfg.lig_radius_cap)
       return fail(CBD_ERR_ARG, "co-scheduled engines must share one model configuration");
@@ -1642,16 +1567,6 @@ int cbd_set_option(cbd_engine* e, const char* name, int64_t value) {
     if (value != 0) e->use_bf16 = 1; else if (e->use_bf16 == 1) e->use_bf16 = 0;
     drop_graphs(e);
     return 0;
-  }
-  if (k == "bf16_roles") {   // bf16 only: cross / receptor groups as three tile slices per layer (captured graphs bake it in)
-#ifdef CBD_EXPERIMENTS
-    e->bf16_roles = (int)std::max<long long>(0, std::min<long long>(2, value));
-    drop_graphs(e);
-    return 0;
-#else
-    if (value == 0) return 0;
-    return fail(CBD_ERR_ARG, "bf16_roles is an experiment of the diagnostic library (tools/diag_lib.py), not part of libcbdock.so");
-#endif
   }
   if (k == "async_setup") {   // cbd_set_complex on a stream of its own, waiting only for this engine's last cbd_sample* launches (see cbd_engine)
     e->async_setup = value != 0;

@@ -40,8 +40,7 @@ namespace cbd {
 template <int IN, int OUT, int VAR, class Ops>
 __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
   constexpr ConvShape S = conv_shape(IN, OUT, true);   // merged vector tails (common.h)
-  constexpr bool STAMPS = VAR == 8 || VAR == 13;     // diagnostics: 13 = the stamps of 8 on the gather pattern of 12
-  constexpr int GV = VAR == 13 ? 12 : VAR;
+  constexpr bool STAMPS = VAR == 8;     // diagnostic (correct results): phase stamps
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* bias_l = lds;                                 // [ntiles][32]
   float* xT = lds + S.ntiles * 32;                     // [80][32] gathered destination rows, transposed
@@ -118,16 +117,13 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
       // stream's table in global memory (its LDS copy is still being written)
       const f32x4* const gb = reinterpret_cast<const f32x4*>(reinterpret_cast<const Frag*>(G.wstream) + (size_t)(S.ntiles + 1) * Ops::TILE_FRAGS);
       const f32x4* const p_s = reinterpret_cast<const f32x4*>(G.psrc + (size_t)src_r * KDIM + 4 * hf);
-      // diagnostics with WRONG results (timing only): VAR 10 reads the destination projection at the aggregating node's row (run-
-      // coherent instead of random), VAR 11 skips both projection gathers, VAR 12 also gathers the node row at the aggregating node
-      const f32x4* const p_d = reinterpret_cast<const f32x4*>(G.pdst + (size_t)(GV >= 10 && GV < 14 ? src_r : dst) * KDIM + 4 * hf);
+      const f32x4* const p_d = reinterpret_cast<const f32x4*>(G.pdst + (size_t)dst * KDIM + 4 * hf);
 #pragma unroll
       for (int m = 0; m < 3; ++m)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 b = gb[8 * m + 2 * q + hf];
-          f32x4 u = b, w = b;
-          if constexpr (GV < 11 || GV == 14) { u = gl(p_s + 8 * m + 2 * q); w = gl(p_d + 8 * m + 2 * q); }
+          const f32x4 u = gl(p_s + 8 * m + 2 * q), w = gl(p_d + 8 * m + 2 * q);
           acc1[m][4 * q + 0] = b.x + u.x + w.x; acc1[m][4 * q + 1] = b.y + u.y + w.y;
           acc1[m][4 * q + 2] = b.z + u.z + w.z; acc1[m][4 * q + 3] = b.w + u.w + w.w;
         }
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
       __builtin_amdgcn_sched_barrier(0);
       Ops::template load_first_part<2, 3>(a, gu, lane);
     }
-    const f32x4* pr = reinterpret_cast<const f32x4*>(G.node_in + (size_t)(GV == 12 ? src_r : dst) * NODE_STRIDE + 40 * hf);
+    const f32x4* pr = reinterpret_cast<const f32x4*>(G.node_in + (size_t)dst * NODE_STRIDE + 40 * hf);
 #pragma unroll
     for (int q = 0; q < 10; ++q) {
       const f32x4 r = gl(pr + q);
@@ -158,8 +154,8 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
 #define CBD_TILE(BOP, NEXT)                                                                         \
   {                                                                                                 \
     const int tn_ = (NEXT);                                                                         \
-    if constexpr (Ops::NODE_PROJ) gemm_tile_u<Ops>(a, gu + (VAR == 9 ? (size_t)0 : (size_t)tn_ * Ops::TILE_FRAGS), lane, bias_l + T * 32, BOP, acc, hf); \
-    else gemm_tile<Ops>(a, gp + (VAR == 9 ? (size_t)0 : (size_t)tn_ * Ops::TILE_FRAGS), bias_l + T * 32, BOP, acc, hf); \
+    if constexpr (Ops::NODE_PROJ) gemm_tile_u<Ops>(a, gu + (size_t)tn_ * Ops::TILE_FRAGS, lane, bias_l + T * 32, BOP, acc, hf); \
+    else gemm_tile<Ops>(a, gp + (size_t)tn_ * Ops::TILE_FRAGS, bias_l + T * 32, BOP, acc, hf); \
     T = tn_;                                                                                        \
   }
 
@@ -180,7 +176,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
   } else {
     // K = 32 edge-attribute product on top of acc1[m]; tile m's registers are refilled with the first second-Linear tile's fragments
     const int tn_ = i_lo < i_hi ? 3 + i_lo : T_vec;
-    const GPtr<Frag> next = gu + (VAR == 9 ? (size_t)0 : (size_t)tn_ * Ops::TILE_FRAGS);
+    const GPtr<Frag> next = gu + (size_t)tn_ * Ops::TILE_FRAGS;
     Ops::template gemm_first_u<0>(a, next, lane, Bx, acc1[0]);
     Ops::set_hidden(h1, 0, acc1[0]);
     if constexpr (STAMPS) st_g0 = stamp();
@@ -425,24 +421,14 @@ __global__ void conv_finalize_multi_kernel(Multi mm, int kind, int xi_in, int xi
   const PoseBatch& PB = fin_locate(mm, blk);
   const int idx = blk * blockDim.x + threadIdx.x;
   const int i = idx / NODE_STRIDE, c = idx % NODE_STRIDE;
-  const bool roles = kind >= FIN_FIRST_R;          // bf16 role split: the cross / receptor groups come with a second 0e slice
-  const int base = roles ? kind - (FIN_FIRST_R - FIN_FIRST) : kind;
-  const int n0 = PB.B * PB.gs.Nl, n1 = (base == FIN_FIRST || base == FIN_MID) ? PB.B * PB.gs.Nr : 0;
+  const int n0 = PB.B * PB.gs.Nl, n1 = (kind == FIN_FIRST || kind == FIN_MID) ? PB.B * PB.gs.Nr : 0;
   if (i >= n0 + n1) return;
   const float* node_in = PB.X[xi_in];
   float* node_out = PB.X[xi_out];
-#ifdef CBD_EXPERIMENTS
-  // (the role split belongs to the bf16 policy: the engine never runs the node-major 0e path with it, use0e is 0 there)
-  if (i < n0) finalize_one(base == FIN_EMB ? PB.fin_emb : roles ? PB.fin_lig_r : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim,
-                           out_dim, 0, use0e != 0);
-  else finalize_one(base == FIN_FIRST ? (roles ? PB.fin_rec_shared_r : PB.fin_rec_shared) : (roles ? PB.fin_rec_r : PB.fin_rec), node_in, node_out,
-                    bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim, PB.gs.rec_off, use0e != 0);
-#else
-  if (i < n0) finalize_one(base == FIN_EMB ? PB.fin_emb : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim, out_dim, 0,
+  if (i < n0) finalize_one(kind == FIN_EMB ? PB.fin_emb : PB.fin_lig, node_in, node_out, bn_scale, bn_mean, bn_bias, i, c, in_dim, out_dim, 0,
                            use0e != 0);
-  else finalize_one(base == FIN_FIRST ? PB.fin_rec_shared : PB.fin_rec, node_in, node_out, bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim,
+  else finalize_one(kind == FIN_FIRST ? PB.fin_rec_shared : PB.fin_rec, node_in, node_out, bn_scale, bn_mean, bn_bias, i - n0, c, in_dim, out_dim,
                     PB.gs.rec_off, use0e != 0);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -611,17 +597,10 @@ static hipError_t launch_one(const ConvArgs& a, int grid, hipStream_t s) {
 #ifdef CBD_DIAG
   // Diagnostic library only (tools/diag_lib.py builds experiments/libcbdock_diag.so with -DCBD_DIAG; the product library holds the
   // VAR = 0 kernels alone and never reads this variable).  CBD_CONV_VARIANT=8: the 74->74 kernel stamps s_memtime / s_memrealtime
-  // (correct results); 14: non-temporal gathers (correct results); 9 .. 13: timing-only bounds with WRONG results -- 9: every tile
-  // re-reads weight tile 0 (the L2 -> register weight stream becomes L1-resident: what a perfect weight-reuse scheme could gain),
-  // 10 .. 12: run-coherent / skipped gathers, 13: the stamps of 8 on the gather pattern of 12.
+  // (correct results); 14: non-temporal gathers (correct results).
   static const int var = getenv("CBD_CONV_VARIANT") ? atoi(getenv("CBD_CONV_VARIANT")) : 0;
   if (IN == 3 && var == 8) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 8 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && var == 9) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 9 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && var == 10) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 10 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && var == 11) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 11 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
   else if (IN == 3 && var == 14) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 14 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && var == 13) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 13 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && var == 12) hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, (IN == 3 ? 12 : 0), OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);
   else
 #endif
   hipLaunchKernelGGL((tp_conv_kernel<IN, OUT, 0, OpsF32>), dim3(grid), dim3(64), lds_bytes, s, a);

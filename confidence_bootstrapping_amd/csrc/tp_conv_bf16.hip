@@ -7,8 +7,8 @@
 //     chains), which halves the weight stream per FLOP and the per-tile fixed costs;
 //   * the bias (fp32) is the C operand of a tile's first MFMA pair, kept in 16 registers that are re-loaded in place: 6 k-steps and
 //     6 KB per tile, no accumulator initialisation (an earlier version spent a 7th k-step on it);
-//   * what bounds this kernel is not the matrix core but everything next to it (in-kernel stamps and timing-only diagnostics,
-//     CBD_BF16_DIAG=1..4): every VALU instruction costs matrix-pipe time, so the CG epilogue was trimmed --
+//   * what bounds this kernel is not the matrix core but everything next to it (in-kernel stamps, CBD_BF16_DIAG=4, and the timing-only
+//     diagnostics of rounds 2-3): every VALU instruction costs matrix-pipe time, so the CG epilogue was trimmed --
 //     -fno-slp-vectorize (packed fp32 FMAs are the most expensive kind), scalar x direction mids factored out of the sums, one-
 //     instruction ReLU, padded slots skipped -- and the per-wave latency phases shortened: gathers in two rounds, vector-block tile
 //     loops fully unrolled so that mids are compile-time constants and their LDS reads batch, run-length reduction with scalar run
@@ -32,10 +32,7 @@
 
 namespace cbd {
 
-// DIAG (timing only, WRONG results; CBD_BF16_DIAG=n): 1 = every tile re-reads weight tile 0 (the weight stream becomes L1-resident),
-// 2 = no CG epilogue (the accumulators are only summed up), 3 = both; 4 = correct results + phase stamps (tools/conv_clock.py bf16);
-// 8 = the bias registers are never re-loaded, 9 = 8 + 1, 16 = no weight or bias re-loads at all (the first tile's registers serve every
-// tile: the kernel without its weight stream), 24 = 16 + 8, 32 = the bias bpermutes are not waited for
+// DIAG (diagnostic library only, CBD_BF16_DIAG=4): correct results + phase stamps (tools/conv_clock.py bf16)
 template <int IN, int OUT, int DIAG = 0>
 __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
   constexpr ConvShape S = conv_shape(IN, OUT, true);   // merged vector tails (common.h), as in tp_conv.hip
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
 #define V2_TILE(BA, BB, NEXT, NEXT2)                                               \
   {                                                                         \
     const int tn_ = (NEXT);                                                 \
-    v2_gemm<DIAG>(a, cb, gp + ((DIAG & 1) ? (size_t)0 : (size_t)tn_ * V2_TILE_FRAGS), gbias + (size_t)(NEXT2) * 32, raw_next, lane, lane4hf, BA, BB, acc0, acc1); \
+    v2_gemm(a, cb, gp + (size_t)tn_ * V2_TILE_FRAGS, gbias + (size_t)(NEXT2) * 32, raw_next, lane, lane4hf, BA, BB, acc0, acc1); \
     T = tn_;                                                                \
   }
   // ---- first Linear (3 tiles): h = ReLU(W1 x + b1), kept in the C/D register layout = B operand of the second Linear
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
     if (m == 2) mfma_operand_guard();   // the first-Linear operands die here without a refill
     v2_set_hidden(h0, m, acc0);
     v2_set_hidden(h1, m, acc1);
-    if constexpr (!(DIAG & 40)) bias_ready(cb);
+    bias_ready(cb);
   }
 
   if constexpr (DIAG == 4) st_t2 = stamp();
@@ -181,7 +178,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
     const GFrag gb0e = (GFrag)reinterpret_cast<const bf16x8*>(reinterpret_cast<const float*>(reinterpret_cast<const bf16x8*>(G.wstream) + (size_t)(S.ntiles + 1) * V2_TILE_FRAGS) + (size_t)(S.ntiles + 1) * 32);
 #pragma unroll
     for (int s3 = 0; s3 < 3; ++s3) ab0e[s3] = gb0e[s3 * 64 + lane];
-    if (vec_on && !(DIAG & 8)) {   // the vector blocks behind this one still take their bias as the C operand: request it now
+    if (vec_on) {   // the vector blocks behind this one still take their bias as the C operand: request it now
       const GPtr<f32x4> gb4 = (GPtr<f32x4>)(gbias + (size_t)T_vec * 32);
 #pragma unroll
       for (int qq = 0; qq < 4; ++qq) {
@@ -203,26 +200,22 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
   //  in scratch memory)
 #define V2_EPI_ALL(Y0, Y1, M0, M1)                                                                                   \
   {                                                                                                                  \
-    if constexpr (DIAG & 2) { o0e0[0] += Y0[0] + M0; o0e1[0] += Y1[0] + M1; } else {                                 \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) { o0e0[r] = fmaf(M0, Y0[r], o0e0[r]); o0e1[r] = fmaf(M1, Y1[r], o0e1[r]); } \
-    }                                                                                                                \
+    _Pragma("unroll") for (int r = 0; r < 16; ++r) { o0e0[r] = fmaf(M0, Y0[r], o0e0[r]); o0e1[r] = fmaf(M1, Y1[r], o0e1[r]); } \
   }
 #define V2_CHAIN_PLAIN(I, X0, X1)                                                                                    \
   {                                                                                                                  \
     const int tn_ = next_of(I);                                                                                      \
-    v2_gemm_p<DIAG, false>(a, cb, gp + ((DIAG & 1) ? (size_t)0 : (size_t)tn_ * V2_TILE_FRAGS), gbias, raw_next, lane, lane4hf, h0, h1, \
+    v2_gemm_p<false>(a, cb, gp + (size_t)tn_ * V2_TILE_FRAGS, gbias, raw_next, lane, lane4hf, h0, h1, \
                     X0, X1, [](int) {});                                                                             \
     T = tn_;                                                                                                         \
   }
 #define V2_CHAIN_EPI(I, X0, X1, Y0, Y1, M0, M1)                                                                      \
   {                                                                                                                  \
     const int tn_ = next_of(I);                                                                                      \
-    v2_gemm_p<DIAG, false>(a, cb, gp + ((DIAG & 1) ? (size_t)0 : (size_t)tn_ * V2_TILE_FRAGS), gbias, raw_next, lane, lane4hf, h0, h1, \
+    v2_gemm_p<false>(a, cb, gp + (size_t)tn_ * V2_TILE_FRAGS, gbias, raw_next, lane, lane4hf, h0, h1, \
                     X0, X1, [&](int q) __attribute__((always_inline)) {                                              \
-                      if constexpr (DIAG & 2) { if (q == 0) { o0e0[0] += Y0[0] + M0; o0e1[0] += Y1[0] + M1; } } else { \
-                        _Pragma("unroll") for (int r = 0; r < 16; ++r)                                               \
-                          if (r >= EPI_LO[q] && r < EPI_LO[q + 1]) { o0e0[r] = fmaf(M0, Y0[r], o0e0[r]); o0e1[r] = fmaf(M1, Y1[r], o0e1[r]); } \
-                      }                                                                                              \
+                      _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                 \
+                        if (r >= EPI_LO[q] && r < EPI_LO[q + 1]) { o0e0[r] = fmaf(M0, Y0[r], o0e0[r]); o0e1[r] = fmaf(M1, Y1[r], o0e1[r]); } \
                     });                                                                                              \
     T = tn_;                                                                                                         \
   }
@@ -321,16 +314,13 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
       // vector-valued mids are evaluated before the chain (LDS latency and the cross products under the MFMAs); the scalar ones are
       // read behind it -- ten more live registers across the chain would spill
       float ma[VEC_TILE_I][3], mb[VEC_TILE_I][3];
-      if constexpr (!(DIAG & 2)) {
 #pragma unroll
-        for (int q = 0; q < VEC_TILE_I; ++q) {
-          const int i = VEC_TILE_I * t + q;
-          if (i >= fan || is_scalar(i)) continue;
-          mid_fn(xc0, i, v0, ma[q]); mid_fn(xc1, i, v1, mb[q]);
-        }
+      for (int q = 0; q < VEC_TILE_I; ++q) {
+        const int i = VEC_TILE_I * t + q;
+        if (i >= fan || is_scalar(i)) continue;
+        mid_fn(xc0, i, v0, ma[q]); mid_fn(xc1, i, v1, mb[q]);
       }
       V2_TILE(h0, h1, T + 1, T + 2 < S.ntiles ? T + 2 : S.ntiles);
-      if constexpr (DIAG & 2) { keep0[0] += acc0[0]; keep1[0] += acc1[0]; if constexpr (!(DIAG & 40)) bias_ready(cb); continue; }
 #pragma unroll
       for (int q = 0; q < VEC_TILE_I; ++q) {
         const int i = VEC_TILE_I * t + q;
@@ -356,7 +346,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
       // parks the accumulators of the scalar tiles in scratch and does their FMAs several tiles later (1 KB of spills per lane)
 #pragma unroll
       for (int o = 0; o < 3; ++o) { pin(s0[o]); pin(s1[o]); }
-      if constexpr (!(DIAG & 40)) bias_ready(cb);
+      bias_ready(cb);
     }
 #pragma unroll
     for (int o = 0; o < 3; ++o)
@@ -398,7 +388,6 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
           }
         }
         V2_TILE(h0, h1, T + 1, T + 2 < S.ntiles ? T + 2 : S.ntiles);
-        if constexpr (DIAG & 2) { k0o0[0] += acc0[0]; k0o1[0] += acc1[0]; if constexpr (!(DIAG & 40)) bias_ready(cb); continue; }
 #pragma unroll
         for (int q = 0; q < VEC_TILE_I; ++q) {
           if (VEC_TILE_I * t + q >= S.fan0o) continue;
@@ -419,7 +408,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
               }
             }
         }
-        if constexpr (!(DIAG & 40)) bias_ready(cb);
+        bias_ready(cb);
       }
     }
   }
@@ -451,8 +440,8 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
   }
   __syncthreads();
   // Run-length sums per aggregating node and 32-edge reduction tile, exactly the pieces of tp_conv_kernel (reduce_runs, tp_conv_dev.h)
-  // a virtual slice writes only the columns it produces (role split, engine.hip: a 0e-only slice the 32 scalar columns, the vector
-  // slice the rest -- the two share the group's piece buffers; a second 0e slice has buffers of its own)
+  // a virtual slice writes only the columns it produces (embedding layers, engine.hip::emb_slices: a 0e-only slice the 32 scalar
+  // columns; every slice has piece buffers of its own)
   const int col_lo = (vec_on && i_lo >= i_hi) ? NS : 0, col_hi = vec_on ? S.out_dim : NS;
 #pragma unroll 1
   for (int sub = 0; sub < 2; ++sub)
@@ -471,17 +460,9 @@ __global__ __launch_bounds__(64, 2) void tp_conv64_kernel(ConvArgs args) {
 template <int IN, int OUT>
 static hipError_t launch_one64(const ConvArgs& a, int grid, hipStream_t s) {
   constexpr int lds_bytes = (2 * V2_SUB_FLOATS + 64) * 4;
-#ifdef CBD_DIAG      // diagnostic library only (tools/diag_lib.py): timing-only variants with WRONG results, 4 = phase stamps
+#ifdef CBD_DIAG      // diagnostic library only (tools/diag_lib.py): CBD_BF16_DIAG=4 = phase stamps (correct results)
   static const int diag = getenv("CBD_BF16_DIAG") ? atoi(getenv("CBD_BF16_DIAG")) : 0;
-  if (IN == 3 && diag == 1) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 1 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 2) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 2 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 4) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 4 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 3) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 3 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 8) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 8 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 9) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 9 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 24) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 24 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 32) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 32 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
-  else if (IN == 3 && diag == 26) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 26 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
+  if (IN == 3 && diag == 4) hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT, (IN == 3 ? 4 : 0)>), dim3(grid), dim3(64), lds_bytes, s, a);
   else
 #endif
   hipLaunchKernelGGL((tp_conv64_kernel<IN, OUT>), dim3(grid), dim3(64), lds_bytes, s, a);

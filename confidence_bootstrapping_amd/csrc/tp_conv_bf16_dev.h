@@ -1,5 +1,5 @@
 // Device code shared by the two bf16 tensor-product kernels (tp_conv_bf16.hip: one wave per workgroup, weight tiles streamed from L2;
-// tp_conv_bf16p.hip: persistent workgroups with a 0e slice's weight tiles resident in LDS): fragment types, operand packing, the MFMA
+// tp_conv_bf16s.hip: persistent workgroups with register-stationary weight tiles): fragment types, operand packing, the MFMA
 // chains with in-place fragment refill.  See tp_conv_bf16.hip for the design notes.
 #pragma once
 #include <type_traits>
@@ -41,7 +41,6 @@ __device__ __forceinline__ void v2_set_hidden(Act6& h, int m, const f32x16& acc)
 //   * fragment q-1 is re-loaded after the MFMA pair of fragment q has been issued -- one pair late, so that even a load that hits in
 //     L1 (~120 cycles) lands after the pair that read the register has started; the bias follows the second pair, the last fragment
 //     its own pair directly.
-template <int DIAG = 0>
 __device__ __forceinline__ void v2_gemm(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFrag next, GPtr<float> next_bias, float& raw_next, int lane,
                                         int lane4hf, const Act6& B0, const Act6& B1, f32x16& acc0, f32x16& acc1) {
   GFrag pa = next;            // uniform: tile base (fragments 0..3: immediate offsets 0..3 KB)
@@ -65,32 +64,30 @@ __device__ __forceinline__ void v2_gemm(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFrag
     if (q == 0) asm volatile("" : "+v"(cb));
     // the next tile's 32 bias floats: ONE dword per lane (lane l gets float l & 31: 256 B through the vector-memory return path
     // instead of the 4 KB of four broadcast dwordx4 loads -- timing-only diagnostics put those at 11 % of the kernel)
-    if (q == 0 && !(DIAG & 8)) raw_new = pc[lane & 31];
-    if (q > 0 && !(DIAG & 16)) a[q - 1] = q - 1 < 4 ? pa[lane + (q - 1) * 64] : pb[lane + (q - 5) * 64];
-    if (q == V2_NFRAG - 1 && !(DIAG & 16)) a[q] = pb[lane + (q - 4) * 64];
+    if (q == 0) raw_new = pc[lane & 31];
+    if (q > 0) a[q - 1] = q - 1 < 4 ? pa[lane + (q - 1) * 64] : pb[lane + (q - 5) * 64];
+    if (q == V2_NFRAG - 1) a[q] = pb[lane + (q - 4) * 64];
     __builtin_amdgcn_sched_barrier(0);
   }
   // ... spread into the accumulator layout through the LDS crossbar (ds_bpermute_b32, no LDS memory): register r of lane half hf is
   // weight row (r & 3) + 8 (r >> 2) + 4 hf.  Issued behind the last pair: pair 0, which read cb as its C operand, has executed long ago,
   // and the tile's CG epilogue covers the crossbar latency.
-  if constexpr (!(DIAG & 8)) {
-    // inline asm: the builtin takes no offset, and hipcc then keeps 16 address registers (spills); with the instruction's offset
-    // field one address register (byte address of lane 4 hf) serves all 16.  The results are NOT tracked by the compiler's waitcnt
-    // insertion: bias_ready() (s_waitcnt lgkmcnt(0)) closes the tile's epilogue before cb is read again.
-    float t[16];
+  // inline asm: the builtin takes no offset, and hipcc then keeps 16 address registers (spills); with the instruction's offset
+  // field one address register (byte address of lane 4 hf) serves all 16.  The results are NOT tracked by the compiler's waitcnt
+  // insertion: bias_ready() (s_waitcnt lgkmcnt(0)) closes the tile's epilogue before cb is read again.
+  float t[16];
 #define CBD_BP4(R, O0, O1, O2, O3)                                                                                      \
-    asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
-                 "\n\tds_bpermute_b32 %2, %4, %5 offset:" #O2 "\n\tds_bpermute_b32 %3, %4, %5 offset:" #O3            \
-                 : "=&v"(t[R]), "=&v"(t[R + 1]), "=&v"(t[R + 2]), "=&v"(t[R + 3]) : "v"(lane4hf), "v"(raw_next))
-    CBD_BP4(0, 0, 4, 8, 12);
-    CBD_BP4(4, 32, 36, 40, 44);
-    CBD_BP4(8, 64, 68, 72, 76);
-    CBD_BP4(12, 96, 100, 104, 108);
+  asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
+               "\n\tds_bpermute_b32 %2, %4, %5 offset:" #O2 "\n\tds_bpermute_b32 %3, %4, %5 offset:" #O3            \
+               : "=&v"(t[R]), "=&v"(t[R + 1]), "=&v"(t[R + 2]), "=&v"(t[R + 3]) : "v"(lane4hf), "v"(raw_next))
+  CBD_BP4(0, 0, 4, 8, 12);
+  CBD_BP4(4, 32, 36, 40, 44);
+  CBD_BP4(8, 64, 68, 72, 76);
+  CBD_BP4(12, 96, 100, 104, 108);
 #undef CBD_BP4
 #pragma unroll
-    for (int r = 0; r < 16; ++r) cb[r] = t[r];
-    raw_next = raw_new;
-  }
+  for (int r = 0; r < 16; ++r) cb[r] = t[r];
+  raw_next = raw_new;
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -100,7 +97,7 @@ __device__ __forceinline__ void v2_gemm(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFrag
 // registers; fragment q - 1, which is dead between its pair and its re-load one pair later, is kept allocated through a fake use so
 // that no VALU temporary can be placed in a register an issued MFMA has not read yet (tp_conv_dev.h).  The next tile's bias is spread
 // behind pair 3 (the raw dword was requested behind pair 0; its lines are hot in L1) and bias_ready() precedes the next chain.
-template <int DIAG = 0, bool BIAS = true, class Epi>
+template <bool BIAS = true, class Epi>
 __device__ __forceinline__ void v2_gemm_p(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFrag next, GPtr<float> next_bias, float& raw_next, int lane,
                                           int lane4hf, const Act6& B0, const Act6& B1, f32x16& acc0, f32x16& acc1, Epi epi) {
   GFrag pa = next;
@@ -126,11 +123,11 @@ __device__ __forceinline__ void v2_gemm_p(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFr
     }
     __builtin_amdgcn_sched_barrier(0);
     if (q == 0 && BIAS) asm volatile("" : "+v"(cb));
-    if (q == 0 && BIAS && !(DIAG & 8)) raw_new = pc[lane & 31];
-    if (q > 0 && !(DIAG & 16)) a[q - 1] = q - 1 < 4 ? pa[lane + (q - 1) * 64] : pb[lane + (q - 5) * 64];
-    if (q == V2_NFRAG - 1 && !(DIAG & 16)) a[q] = pb[lane + (q - 4) * 64];
+    if (q == 0 && BIAS) raw_new = pc[lane & 31];
+    if (q > 0) a[q - 1] = q - 1 < 4 ? pa[lane + (q - 1) * 64] : pb[lane + (q - 5) * 64];
+    if (q == V2_NFRAG - 1) a[q] = pb[lane + (q - 4) * 64];
     __builtin_amdgcn_sched_barrier(0);
-    if (q == 3 && BIAS && !(DIAG & 8)) {
+    if (q == 3 && BIAS) {
       float t[16];
 #define CBD_BP4(R, O0, O1, O2, O3)                                                                                      \
       asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
@@ -148,7 +145,7 @@ __device__ __forceinline__ void v2_gemm_p(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFr
     if (q < V2_NFRAG - 1) asm volatile("" ::"v"(a[q]));   // fragment q stays allocated until its re-load behind pair q + 1
     __builtin_amdgcn_sched_barrier(0);
   }
-  if constexpr (BIAS && !(DIAG & 8)) raw_next = raw_new;
+  if constexpr (BIAS) raw_next = raw_new;
 }
 
 // closes a tile: the ds_bpermute results of v2_gemm (the next tile's bias registers) have landed

@@ -845,7 +845,7 @@ __global__ __launch_bounds__(SW_WAVES * 64, 1) void tp_conv64s_kernel(ConvArgs a
 
 // a: the edge groups of a 74 -> 74 layer (whole tile chains); n_wg: workgroups (<= CUs).  Roles = distinct weight streams.
 // Role table of a launch: one role per distinct FCBlock (weight stream) among its groups.  false: the launch does not fit this kernel --
-// virtual slices of the role split, or more than S_MAX_ROLES FCBlocks (cannot happen through cbd_sample_multi, which wants shared weights:
+// virtual slices, or more than S_MAX_ROLES FCBlocks (cannot happen through cbd_sample_multi, which wants shared weights:
 // four roles per launch; the check keeps the kernel's table safe whatever builds the arguments).
 static bool s_role_table(const ConvArgs& a, RoleTableS& rt) {
   for (int g = 0; g < a.n_groups; ++g) {

@@ -202,14 +202,13 @@ def test_config_c4_bf16_as_specified(model_args, tables):
 
 
 def test_product_library_refuses_the_role_split_experiment(model_args):
-    """The bf16 role split (correct, slower) is compiled into the diagnostic library only (tools/diag_lib.py,
-    experiments/); the product library refuses the option loudly instead of silently ignoring it.  Its own test: experiments/test_role_split.py."""
+    """The bf16 role split (correct, slower) has been removed from the tree; the library refuses the option
+    loudly, as the unknown option it now is, instead of silently ignoring it."""
     from confidence_bootstrapping_amd.synthetic import make_workload
     model, _ = model_args
     eng = model.engine()
     eng.set_complex(make_workload("tiny"))
-    eng.set_option("bf16_roles", 0)
-    with pytest.raises(RuntimeError, match="diagnostic library"):
+    with pytest.raises(RuntimeError, match="unknown option 'bf16_roles'"):
         eng.set_option("bf16_roles", 1)
 
 

@@ -289,16 +289,26 @@ def test_timed_region_stats_cuts_the_trace_between_the_markers(tmp_path):
 
 
 def test_diagnostic_library_still_builds():
-    """experiments/ is not linked into the product, so nothing else notices when a header change breaks it (round 6: reduce_runs' new
-    template parameters broke experiments/csrc/tp_conv_bf16p.hip unnoticed for hours).  Incremental build of the diagnostic twin
-    (tools/diag_lib.py: the product sources with -DCBD_DIAG -DCBD_EXPERIMENTS + experiments/csrc); it must export the whole C ABI too."""
+    """The diagnostic twin is not linked into the product, so nothing else notices when a change breaks its #ifdef CBD_DIAG code.
+    Incremental build of the twin (tools/diag_lib.py: the product sources with -DCBD_DIAG); it must export the whole C ABI too, and
+    it holds no kernel that computes wrong results: the only diagnostic instantiations are the phase stamps / non-temporal gathers of
+    tp_conv_kernel (VAR 8, 14) and the phase stamps of tp_conv64_kernel (DIAG 4)."""
     import ctypes
+    import subprocess
     sys_path = os.path.join(ROOT)
     import sys
     if sys_path not in sys.path:
         sys.path.insert(0, sys_path)
     from tools import diag_lib
     from confidence_bootstrapping_amd import engine
-    lib = ctypes.CDLL(diag_lib.build())
+    path = diag_lib.build()
+    lib = ctypes.CDLL(path)
     for name in engine.SYMBOLS:
         assert getattr(lib, name) is not None
+    names = subprocess.run(["nm", "-C", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    seen = set()
+    for m in re.finditer(r"__device_stub__(tp_conv_kernel|tp_conv64_kernel)<([^>]*)>", names):
+        var = m.group(2).split(",")[2].strip()
+        assert var in (("0", "8", "14") if m.group(1) == "tp_conv_kernel" else ("0", "4")), m.group(0)
+        seen.add((m.group(1), var))
+    assert {("tp_conv_kernel", "0"), ("tp_conv_kernel", "8"), ("tp_conv_kernel", "14"), ("tp_conv64_kernel", "0"), ("tp_conv64_kernel", "4")} <= seen, seen

@@ -4,13 +4,13 @@ import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.diag_lib import use_diag_library
-use_diag_library()      # phase stamps / timing-only variants / role split exist in experiments/libcbdock_diag.so only
+use_diag_library()      # phase stamps exist in experiments/libcbdock_diag.so only
 from confidence_bootstrapping_amd.synthetic import make_workload
 from confidence_bootstrapping_amd.utils import make_score_model
 from confidence_bootstrapping_amd.engine import DockEngine, make_steps
 from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule
 BF16 = os.environ.get("CBD_BF16_DIAG") == "4"
-assert BF16 or os.environ.get("CBD_CONV_VARIANT") in ("8", "13")
+assert BF16 or os.environ.get("CBD_CONV_VARIANT") == "8"
 dev = torch.device("cuda:0")
 model, args = make_score_model(seed=0)
 cplx = make_workload("c4_large_pocket" if BF16 else "c2_dockgen_median")

@@ -5,7 +5,7 @@ import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.diag_lib import use_diag_library
-use_diag_library()      # phase stamps / timing-only variants / role split exist in experiments/libcbdock_diag.so only
+use_diag_library()      # phase stamps exist in experiments/libcbdock_diag.so only
 os.environ.setdefault("CBD_BF16_DIAG", "4")
 from confidence_bootstrapping_amd.synthetic import make_workload, BENCH_GEOMETRY
 from confidence_bootstrapping_amd.utils import make_score_model

@@ -6,7 +6,6 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout 1800 python -m pytest tests -q -m gpu > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
-timeout 600 python -m pytest experiments/test_role_split.py -q > $OUT/pytest_experiments.log 2>&1; tail -2 $OUT/pytest_experiments.log
 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_lines.json 2> $OUT/bench_line.err; tail -c 600 $OUT/bench_lines.json
 bash tools/profile_default.sh $TAG > $OUT/profile_default.log 2>&1
 bash tools/profile_c4_bf16.sh $TAG > $OUT/profile_c4.log 2>&1
