@@ -407,18 +407,77 @@ def get_lig_graph(mol: Mol, complex_graph):
         complex_graph["ligand"].pos = torch.from_numpy(mol.GetConformer().GetPositions()).float()
 
 
-def get_lig_graph_with_matching(mol_, complex_graph, popsize=None, maxiter=None, matching=False, keep_original=False, num_conformers=1,
-                                remove_hs=False, tries=10, skip_matching=False):
-    """Reference process_mols.py:609-657, the `matching=False` branch (poses as given in the file; what inference on holo ligands
-    uses).  Conformer generation + torsion matching (`matching=True`) is rdkit's ETKDG and differential evolution: not built."""
-    if matching:
-        raise NotImplementedError("conformer matching needs rdkit (ETKDG embedding); call with matching=False")
-    complex_graph.rmsd_matching = 0
+def _lig_graph_from_matched_conformers(mol_, complex_graph, conformers, popsize, maxiter, keep_original, num_conformers, remove_hs, tries,
+                                       skip_matching):
+    """The `matching=True` branch of reference process_mols.py:610-655 for conformers supplied by the caller."""
+    import copy
+    from . import conformer_matching as cm
+    n_all = mol_.GetNumAtoms()
+    if isinstance(conformers, Mol):
+        conformers = [conformers]
+    confs = [np.asarray(c.GetConformer().GetPositions() if isinstance(c, Mol) else c, dtype=np.float64) for c in conformers]
+    if not confs or any(c.shape != (n_all, 3) for c in confs):
+        raise ValueError(f"conformers must be a non-empty sequence of [{n_all}, 3] coordinates in the atom order of the molecule")
+    mol = copy.deepcopy(mol_)
     if remove_hs:
-        mol_ = _remove_hs(mol_ if mol_.perceived else perceive(mol_))
+        if not mol.perceived:
+            perceive(mol)
+        tagged = copy.deepcopy(mol)                      # which atoms stay: carry the atom numbers through as coordinates
+        tagged.pos = np.repeat(np.arange(n_all, dtype=np.float64)[:, None], 3, axis=1)
+        keep = _remove_hs(tagged).pos[:, 0].astype(np.int64)
+        mol = _remove_hs(mol)
+        confs = [c[keep] for c in confs]
+    holo = mol.GetConformer().GetPositions()
     if keep_original:
-        complex_graph["ligand"].orig_pos = mol_.GetConformer().GetPositions()
-    get_lig_graph(mol_, complex_graph)
+        complex_graph["ligand"].orig_pos = holo
+    rotable_bonds = cm.get_torsion_angles(mol)
+    if rotable_bonds and not skip_matching:
+        topo = HeteroData()
+        get_lig_graph(mol, topo)
+        _, mask_rotate = get_transformation_mask(topo)
+        confs, _, _ = cm.optimize_rotatable_bonds(np.stack(confs), holo, rotable_bonds, mask_rotate,
+                                                  popsize=15 if popsize is None else popsize, maxiter=500 if maxiter is None else maxiter)
+    picked = None
+    for i in range(num_conformers):
+        group = confs[i * tries:(i + 1) * tries]
+        if len(group) == 0:
+            raise ValueError(f"{len(confs)} conformers do not cover {num_conformers} groups of {tries}")
+        aligned = [cm.rigid_align(c, holo) for c in group]
+        rmsds = [r for _, r in aligned]
+        best = aligned[int(np.argmin(rmsds))][0]
+        if i == 0:
+            complex_graph.rmsd_matching = min(rmsds)
+            picked = copy.deepcopy(mol)
+            picked.pos = best
+            get_lig_graph(picked, complex_graph)
+        else:
+            if torch.is_tensor(complex_graph["ligand"].pos):
+                complex_graph["ligand"].pos = [complex_graph["ligand"].pos]
+            complex_graph["ligand"].pos.append(torch.from_numpy(best).float())
+    return picked
+
+
+def get_lig_graph_with_matching(mol_, complex_graph, popsize=None, maxiter=None, matching=False, keep_original=False, num_conformers=1,
+                                remove_hs=False, tries=10, skip_matching=False, conformers=None):
+    """Reference process_mols.py:609-657.  `matching=False`: poses as given in the file (what inference on holo ligands uses).
+    `matching=True`: the reference embeds `tries` fresh conformers per requested conformer with rdkit's ETKDG -- not built -- and
+    matches each to the holo pose; here the conformers come from the caller.  `conformers`: a sequence of [N, 3] arrays (or of
+    `Mol`s, or one `Mol`) in the atom order of `mol_`, `num_conformers` consecutive groups of `tries` (a shorter last group is
+    taken as it is).  Every one is torsion-matched on the GPU (datasets/conformer_matching.py) unless `skip_matching` or the molecule
+    has no rotatable bond, aligned onto the holo pose, and the one with the lowest RMSD of each group is kept: the first builds the
+    graph (`rmsd_matching` = its RMSD), the others are appended to ['ligand'].pos.  Returns the molecule with the kept coordinates."""
+    if matching:
+        if conformers is None:
+            raise NotImplementedError("generating conformers needs rdkit (ETKDG embedding); pass conformers=..., or call with matching=False")
+        mol_ = _lig_graph_from_matched_conformers(mol_, complex_graph, conformers, popsize, maxiter, keep_original, num_conformers,
+                                                  remove_hs, tries, skip_matching)
+    else:
+        complex_graph.rmsd_matching = 0
+        if remove_hs:
+            mol_ = _remove_hs(mol_ if mol_.perceived else perceive(mol_))
+        if keep_original:
+            complex_graph["ligand"].orig_pos = mol_.GetConformer().GetPositions()
+        get_lig_graph(mol_, complex_graph)
     edge_mask, mask_rotate = get_transformation_mask(complex_graph)
     complex_graph["ligand"].edge_mask = torch.tensor(edge_mask)
     complex_graph["ligand"].mask_rotate = mask_rotate

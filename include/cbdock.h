@@ -211,6 +211,34 @@ int cbd_knn_graph(int32_t n, int32_t k, const float* pos_dev, int32_t* nbr_out_d
 int cbd_radius_neighbors(int32_t n, float cutoff, int32_t cap, const float* pos_dev, int32_t* idx_out_dev, int32_t* cnt_out_dev,
                          void* stream);
 
+/* Torsion matching of ligand conformers (reference datasets/conformer_matching.py:30-61 as used at
+ * datasets/process_mols.py:624-650, where scipy's differential evolution drives rdkit's SetDihedralRad + AlignMol in a Python loop).
+ * A matching problem: probe and target coordinates [Nl][3] of one molecule, R torsion bonds as quadruples (k, u, v, l) -- u-v is the
+ * bond, k / l the atoms that define its dihedral -- and mask_rotate [R][Nl] (0/1, the side of bond r that turns; exactly one of k, l
+ * lies on it).  The objective f(theta) is the RMSD to the target, after optimal rigid alignment, of the probe with its R dihedrals
+ * SET to theta (IUPAC sign: cis 0, trans pi, looking down u -> v a clockwise turn of l relative to k is positive).
+ * n_problems problems go out in one launch.  All arrays are padded to the launch's largest sizes: probe / target [n][max_nl][3],
+ * quads [n][max_r][4], mask_rotate [n][max_r][max_nl], theta [n][.][max_r]; nl_dev / r_dev [n] give each problem's own Nl and R (NULL:
+ * max_nl / max_r for all).  Limits: 1 <= R <= 32, 1 <= Nl <= 256, popsize * max_r <= 512, else CBD_ERR_ARG (R = 0 needs no kernel:
+ * the answer is the alignment RMSD of the probe).  A problem whose own sizes or atom indices are out of range reads nothing out of
+ * bounds and gets NaN (and -1 generations).  Device pointers; asynchronous on `stream`.
+ * cbd_match_score: score_out [n][n_theta] = f of the given theta vectors.
+ * cbd_match_torsions: the whole differential evolution per problem on the device -- Latin-hypercube population of
+ * max(5, popsize * R) individuals in [-pi, pi), best1bin, mutation factor drawn once per generation from [mutation_lo, mutation_hi),
+ * binomial crossover with probability `recombination`, greedy replacement of the whole generation at once, stop after maxiter
+ * generations or when std(fitness) <= tol * |mean(fitness)| (scipy's defaults with updating='deferred'; one deliberate difference: a
+ * mutant outside the bounds is wrapped periodically instead of re-drawn).  maxiter = 0 returns the best initial individual.  Random
+ * numbers are a hash of (seed, problem id, generation, individual, dimension, purpose) with problem_id_dev [n] (NULL: the index in
+ * the launch), so a problem's result does not depend on what else is launched with it; bitwise repeatable.  Outputs: theta_out
+ * [n][max_r], fitness_out [n], generations_out [n] (generations run). */
+int cbd_match_score(int32_t n_problems, int32_t max_nl, int32_t max_r, int32_t n_theta, const int32_t* nl_dev, const int32_t* r_dev,
+                    const float* probe_dev, const float* target_dev, const int32_t* quads_dev, const uint8_t* mask_rotate_dev,
+                    const float* theta_dev, float* score_out_dev, void* stream);
+int cbd_match_torsions(int32_t n_problems, int32_t max_nl, int32_t max_r, const int32_t* nl_dev, const int32_t* r_dev, const float* probe_dev,
+                       const float* target_dev, const int32_t* quads_dev, const uint8_t* mask_rotate_dev, const int32_t* problem_id_dev,
+                       uint64_t seed, int32_t popsize, int32_t maxiter, float mutation_lo, float mutation_hi, float recombination, float tol,
+                       float* theta_out_dev, float* fitness_out_dev, int32_t* generations_out_dev, void* stream);
+
 /* ============================ all-atom CONFIDENCE model ===========================================
  * Replaces, for the shipped workdir/pretrained_confidence architecture, the confidence branch of
  * utils/sampling.py:240-261: crop_beyond (utils/utils.py:395-420) + set_time(0) + the all-atom
