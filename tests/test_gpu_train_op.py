@@ -221,6 +221,40 @@ def test_fused_score_loss_equals_the_torch_form():
             assert np.isnan(va[0]) and np.isnan(vb[0])
 
 
+@pytest.mark.parametrize("B,T", [(200, 1500), (86, 257)])
+def test_fused_score_loss_strided_loops_against_fp64(B, T):
+    """score_loss_kernel is ONE block of 256 threads striding over 3 B and T elements; the test above (3 B = 21, T = 43) never gives a
+    thread a second element.  Here a thread takes up to three / six (B = 200, T = 1500), or exactly two threads take a second one
+    (3 B = 258, T = 257).  Against training.loss_from_targets on float64 CPU tensors (the fused path is taken for float32 only, so this
+    is the torch-op form in double): the 11 values to 1e-6 relative -- the sums are double in the kernel, what remains is the fp32
+    arithmetic of each term -- and the three gradients to 8 u (u = 2^-24) of their largest entry: four fp32 roundings per element,
+    with a factor 2 of margin."""
+    from confidence_bootstrapping_amd.training import loss_from_targets
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1000 + B)
+    r = lambda *s: torch.randn(*s, generator=g)
+    tg = {"tr_score": r(B, 3), "tr_sigma": (r(B, 1).abs() + 0.3), "rot_score": r(B, 3), "rot_score_norm": (r(B, 1).abs() + 0.5),
+          "tor_score": r(T), "tor_score_norm2": (r(T).abs() + 0.2)}
+    preds = [r(B, 3), r(B, 3), r(T)]
+
+    def run(cast):
+        p = [cast(t).requires_grad_() for t in preds]
+        out = loss_from_targets(p[0], p[1], p[2], {k: cast(v) for k, v in tg.items()}, 0.4, 0.35, 0.25, True, False)
+        (out[0] * 1.7).sum().backward()
+        return [float(o.detach()) for o in out], [q.grad for q in p]
+    va, ga = run(lambda t: t.to(dev))
+    vb, gb = run(lambda t: t.double())
+    assert len(va) == 11 and len(vb) == 11 and all(q.dtype == torch.float64 and not q.is_cuda for q in gb)
+    print(f"score loss B={B} T={T}: values rel " + " ".join(f"{abs(x - y) / abs(y):.1e}" if y else f"{abs(x - y):.1e}" for x, y in zip(va, vb)))
+    print("  gradients, error / (u * largest entry): " + " ".join(
+        f"{float((x.double().cpu() - y).abs().max()) / (2.0 ** -24 * float(y.abs().max())):.2f}" for x, y in zip(ga, gb)))
+    for k, (x, y) in enumerate(zip(va, vb)):
+        assert abs(x - y) <= 1e-6 * abs(y), (k, x, y)
+    for k, (x, y) in enumerate(zip(ga, gb)):
+        assert x.shape == y.shape
+        assert float((x.double().cpu() - y).abs().max()) <= 8 * 2.0 ** -24 * float(y.abs().max()), k
+
+
 def test_fused_heads_equal_the_torch_forms():
     """cbd_center_tp_* / cbd_bond_tp_* (train_ops.CenterTpFn / BondTpFn) against the torch-op forms of the two e3nn heads
     (train_forward.center_tensor_product / bond_tensor_product, which the reference's training step g11 pins): outputs and the gradients
