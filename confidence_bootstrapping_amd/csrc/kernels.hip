@@ -3,6 +3,7 @@
 // Each kernel cites the reference lines it replaces.  64-wide wavefronts throughout (ballot = 64-bit).
 #include "kernels.h"
 #include "device_util.h"
+#include "pose_math.h"
 
 namespace cbd {
 
@@ -564,27 +565,7 @@ hipError_t launch_bond_nb(const Multi& m, float lig_r, int cap, hipStream_t s) {
 // rigid update about the centroid, R sequential torsion rotations (utils/torsion.py:75-90, order dependent),
 // Kabsch re-alignment of the flexible pose onto the rigid one (utils/geometry.py:246-276; closed form via Horn's
 // quaternion + fp64 Jacobi, tests/test_kernel_math.py::horn_rotation).  One wave per sample, one lane per atom.
-CBD_DEV void axis_angle_to_matrix(float ax, float ay, float az, float (&R)[9]) {
-  // via quaternion, incl. the |angle| < 1e-6 series branch (utils/geometry.py:39-86)
-  const float ang = sqrtf(ax * ax + ay * ay + az * az);
-  const float half = 0.5f * ang;
-  const float k = fabsf(ang) < 1e-6f ? 0.5f - (ang * ang) / 48.f : sinf(half) / ang;
-  const float r = cosf(half), i = ax * k, j = ay * k, kk = az * k;
-  const float two_s = 2.0f / (r * r + i * i + j * j + kk * kk);
-  R[0] = 1 - two_s * (j * j + kk * kk); R[1] = two_s * (i * j - kk * r);     R[2] = two_s * (i * kk + j * r);
-  R[3] = two_s * (i * j + kk * r);     R[4] = 1 - two_s * (i * i + kk * kk); R[5] = two_s * (j * kk - i * r);
-  R[6] = two_s * (i * kk - j * r);     R[7] = two_s * (j * kk + i * r);     R[8] = 1 - two_s * (i * i + j * j);
-}
-
-CBD_DEV float wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-CBD_DEV double wave_sum_d(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
+// axis_angle_to_matrix, wave_sum, wave_sum_d: pose_math.h (shared with noise_transform.hip)
 __global__ __launch_bounds__(64) void pose_update_kernel(Multi mm, int step, SdeCoefs cf, int use_coefs, int with_torsion) {
   extern __shared__ float sp[];   // [Nl][3] flexible pose, [Nl][3] rigid pose
   int b;

@@ -7,11 +7,19 @@
   data.tor_sigma_edge, complex_t / node_t set to t.
 Host-side like the reference (it runs in the loader, one complex at a time, O(Nl) work); `time_independent`,
 `crop_beyond_cutoff`, all-atom and asynchronous schedules are outside the hot path's scope and raise.
+
+Opt-in device path for a whole batch: `NoiseTransform.draw` makes the draws and sets the targets of one item without moving its pose,
+`NoiseTransform.apply_noise_batch` draws for every item of a list in order (so the generators advance exactly as under sequential
+`__call__`s), packs the ragged batch -- different ligands, each with its own Nl, R and mask_rotate -- into one staging buffer, uploads
+it once and moves all poses with one `cbd_noise_conformers` launch (csrc/noise_transform.hip); each item's `pos` becomes its slice
+of the device output.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import random
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -19,6 +27,40 @@ import torch
 from .. import so3, torus
 from ..diffusion_utils import set_time
 from ..sampling import _mask_rotate_of, modify_conformer_torsion_angles
+
+
+MAX_ATOMS, MAX_TORSIONS = 512, 128      # capacity of cbd_noise_conformers per ligand (include/cbdock.h)
+
+
+def pack_mask_rotate(mask_rotate) -> np.ndarray:
+    """bool [R, Nl] -> uint32 [R, ceil(Nl / 32)], atom a at bit a % 32 of word a // 32 (the layout cbd_noise_conformers reads)."""
+    m = np.asarray(mask_rotate, dtype=bool)
+    m = m.reshape(0, 0) if m.ndim != 2 else m
+    r, nl = m.shape
+    words = (nl + 31) // 32
+    padded = np.zeros((r, words * 32), dtype=bool)
+    padded[:, :nl] = m
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4").reshape(r, words).astype(np.uint32, copy=False)
+
+
+def unpack_mask_rotate(bits, nl) -> np.ndarray:
+    """inverse of pack_mask_rotate -> bool [R, nl]"""
+    b = np.ascontiguousarray(np.asarray(bits, dtype="<u4"))
+    return np.unpackbits(b.view(np.uint8), axis=1, bitorder="little")[:, :nl].astype(bool)
+
+
+def pack_ligand(data):
+    """(rot_edge int32 [R, 2], mask_bits uint32 [R, ceil(Nl / 32)]) of one item: the ends (u, v) of its rotatable bonds in edge_mask
+    order -- the rows modify_conformer hands to modify_conformer_torsion_angles -- and its packed mask_rotate."""
+    lig = data["ligand"]
+    nl = int(lig.pos.shape[0]) if torch.is_tensor(lig.pos) else int(lig.num_nodes)
+    ei = data["ligand", "ligand"].edge_index.T[lig.edge_mask]
+    edges = np.ascontiguousarray(ei.cpu().numpy().astype(np.int32)).reshape(-1, 2)
+    mask = _mask_rotate_of(data)
+    mask = mask.reshape(len(edges), nl) if mask.size else np.zeros((len(edges), nl), dtype=bool)
+    if mask.shape != (len(edges), nl):
+        raise ValueError(f"mask_rotate {mask.shape} does not match {len(edges)} rotatable bonds x {nl} atoms")
+    return edges, pack_mask_rotate(mask)
 
 
 def axis_angle_to_matrix(aa: torch.Tensor) -> torch.Tensor:
@@ -98,6 +140,95 @@ class NoiseTransform:
             t2 = self.minimum_t + np.random.beta(self.alpha, self.beta) * (1 - self.minimum_t)
             t = choice * t1 + (1 - choice) * t2
         return t, t, t, t
+
+    def draw(self, data):
+        """Everything apply_noise does except moving the pose: the time, the three updates from the same generators in the same order,
+        set_time and the score targets.  -> (tr_update float32 [1, 3], rot_update float64 [3], torsion_updates float64 [R] or None)."""
+        t_tr, t_rot, t_tor, t = self.get_time()
+        if not torch.is_tensor(data["ligand"].pos):
+            data["ligand"].pos = random.choice(data["ligand"].pos)
+        tr_sigma, rot_sigma, tor_sigma = self.t_to_sigma(t_tr, t_rot, t_tor)
+        set_time(data, t, t_tr, t_rot, t_tor, 1, self.all_atom, False, device=None)
+        tr_update = torch.normal(mean=0, std=tr_sigma, size=(1, 3))
+        rot_update = so3.sample_vec(eps=rot_sigma)
+        n_tor = int(data["ligand"].edge_mask.sum())
+        torsion_updates = np.random.normal(loc=0.0, scale=tor_sigma, size=n_tor)
+        torsion_updates = None if self.no_torsion else torsion_updates
+        data.tr_score = -tr_update / tr_sigma ** 2
+        data.rot_score = torch.from_numpy(so3.score_vec(vec=rot_update, eps=rot_sigma)).float().unsqueeze(0)
+        data.tor_score = None if self.no_torsion else torch.from_numpy(torus.score(torsion_updates, tor_sigma)).float()
+        data.tor_sigma_edge = None if self.no_torsion else np.ones(n_tor) * tor_sigma
+        if data["ligand"].pos.shape[0] == 1:
+            data.rot_score = data.rot_score * 0   # a single atom has no orientation
+        return tr_update, rot_update, torsion_updates
+
+    _PACK_CACHE_ENTRIES = 4096
+
+    def _packed(self, data):
+        """pack_ligand(data), cached per ligand: the buffer hands out shallow copies, so the many poses of one ligand share the SAME
+        mask_rotate / edge_index / edge_mask objects; an entry holds them (their ids cannot be recycled) and is checked by identity."""
+        cache = self.__dict__.setdefault("_pack_cache", OrderedDict())
+        lig, bonds = data["ligand"], data["ligand", "ligand"]
+        refs = (lig.mask_rotate, bonds.edge_index, lig.edge_mask)
+        key = tuple(id(r) for r in refs)
+        hit = cache.get(key)
+        if hit is not None and all(a is b for a, b in zip(hit[0], refs)):
+            cache.move_to_end(key)
+            return hit[1]
+        packed = pack_ligand(data)
+        cache[key] = (refs, packed)
+        while len(cache) > self._PACK_CACHE_ENTRIES:
+            cache.popitem(last=False)
+        return packed
+
+    def apply_noise_batch(self, data_list, device):
+        """`__call__` for a list of items with the poses moved on the GPU: draws per item in list order, ONE upload of the packed
+        ragged batch, ONE cbd_noise_conformers launch on the current stream; every item's `['ligand'].pos` is then its slice of the
+        device output (fp32, on `device`).  An item over the kernel's capacity (Nl > 512 or R > 128) is moved by the host
+        `modify_conformer` and stays on the host.  There is no CPU path: `device` must be a GPU.  -> data_list"""
+        from .. import engine
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("apply_noise_batch moves the poses on the MI355X (cbd_noise_conformers); use __call__ per item on the host")
+        lib = engine.load_library()
+        fit = []
+        for d in data_list:
+            tr_u, rot_u, tor_u = self.draw(d)
+            nl, n_tor = int(d["ligand"].pos.shape[0]), int(d["ligand"].edge_mask.sum())
+            if nl > MAX_ATOMS or n_tor > MAX_TORSIONS:
+                modify_conformer(d, tr_u, torch.from_numpy(rot_u).float(), tor_u)
+            else:
+                fit.append((d, tr_u, rot_u, tor_u, nl, n_tor) + self._packed(d))
+        if not fit:
+            return data_list
+        n = len(fit)
+        nls, rs = np.asarray([f[4] for f in fit], dtype=np.int64), np.asarray([f[5] for f in fit], dtype=np.int64)
+        ptr = lambda sizes: np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        lig_ptr, rot_ptr, mask_ptr = ptr(nls), ptr(rs), ptr(rs * ((nls + 31) // 32))
+        with_tor = not self.no_torsion
+        # one staging buffer of 4-byte words: the three prefix sums, the bond ends, the packed masks, then the float32 parts
+        parts = [lig_ptr, rot_ptr, mask_ptr,
+                 np.concatenate([f[6].reshape(-1) for f in fit]), np.concatenate([f[7].reshape(-1) for f in fit]).view(np.int32),
+                 np.concatenate([f[0]["ligand"].pos.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1) for f in fit]).view(np.int32),
+                 np.concatenate([f[1].numpy().astype(np.float32, copy=False).reshape(-1) for f in fit]).view(np.int32),
+                 np.concatenate([np.asarray(f[2], dtype=np.float32).reshape(-1) for f in fit]).view(np.int32),
+                 (np.concatenate([np.asarray(f[3], dtype=np.float32).reshape(-1) for f in fit]) if with_tor else np.zeros(0, np.float32)).view(np.int32)]
+        offs = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
+        host = torch.empty(int(offs[-1]), dtype=torch.int32, pin_memory=True)
+        np.concatenate(parts, out=host.numpy())
+        with torch.cuda.device(dev):
+            staged = host.to(dev, non_blocking=True)
+            out = torch.empty(int(lig_ptr[-1]), 3, dtype=torch.float32, device=dev)
+            at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k])) if offs[k + 1] > offs[k] else None    # part k, NULL when empty
+            rc = lib.cbd_noise_conformers(n, int(nls.max()), int(rs.max()), at(0), at(5), at(1), at(3), at(2), at(4), at(6), at(7),
+                                          at(8) if with_tor else None, C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
+        # `staged` is read by the kernel just enqueued on the stream it was allocated on: the caching allocator orders its reuse behind it
+        for f, a0, a1 in zip(fit, lig_ptr[:-1], lig_ptr[1:]):
+            f[0]["ligand"].pos = out[int(a0):int(a1)]
+        return data_list
 
     def apply_noise(self, data, t_tr, t_rot, t_tor, t, tr_update=None, rot_update=None, torsion_updates=None):
         if not torch.is_tensor(data["ligand"].pos):

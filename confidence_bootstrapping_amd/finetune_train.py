@@ -146,10 +146,13 @@ def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_di
 
 
 class _Loader:
-    """DataListLoader stand-in: shuffled lists of `batch_size` transformed buffer items per epoch."""
+    """DataListLoader stand-in: shuffled lists of `batch_size` transformed buffer items per epoch.  With `batch_transform` the loader
+    fetches the UN-transformed items (`dataset.get`) and hands each batch's list to it once -- NoiseTransform.apply_noise_batch, which
+    noises the whole batch on the GPU; same shuffle, same item order."""
 
-    def __init__(self, dataset, batch_size, shuffle=True, drop_last=False):
+    def __init__(self, dataset, batch_size, shuffle=True, drop_last=False, batch_transform=None):
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
+        self.batch_transform = batch_transform
 
     def __iter__(self):
         n = len(self.dataset)
@@ -158,7 +161,10 @@ class _Loader:
             idx = order[i:i + self.batch_size]
             if self.drop_last and len(idx) < self.batch_size:
                 break
-            yield [self.dataset[int(k)] for k in idx]
+            if self.batch_transform is None:
+                yield [self.dataset[int(k)] for k in idx]
+            else:
+                yield self.batch_transform([self.dataset.get(int(k)) for k in idx])
 
     def __len__(self):
         n = len(self.dataset)
@@ -190,7 +196,11 @@ def inference_finetune(args, model, filtering_model, filtering_args, filtering_c
                         metrics[k].append(m[k])
                 complexes.extend(kept)
             finetune_dataset.add_complexes(complexes)
-            loader = _Loader(finetune_dataset, args.batch_size, shuffle=True, drop_last=getattr(args, "dataloader_drop_last", False))
+            batch_transform = None
+            if getattr(args, "device_noise", False):       # opt-in: noise each batch with one launch instead of item by item on the host
+                batch_transform = partial(finetune_dataset.transform.apply_noise_batch, device=device)
+            loader = _Loader(finetune_dataset, args.batch_size, shuffle=True, drop_last=getattr(args, "dataloader_drop_last", False),
+                             batch_transform=batch_transform)
             logs.update({"targetinf_" + k: (float(np.mean(v)) if v else None) for k, v in metrics.items()})
             logs["kept"] = len(complexes)
             logs["buffer"] = len(finetune_dataset.complexes)

@@ -75,7 +75,9 @@ def collate(data_list: List[HeteroData], device, keep=None) -> Batch:
     t_host = {k: torch.cat([torch.as_tensor(d.complex_t[k], dtype=torch.float32).reshape(-1) for d in data_list]) for k in ("tr", "rot", "tor")}
     eo = np.concatenate([[0], np.cumsum(ne_l)[:-1]])
     rot = np.concatenate([np.flatnonzero(d["ligand"].edge_mask.numpy()) + o for d, o in zip(data_list, eo)]).astype(np.int64)
-    fparts = [d["ligand"].pos.reshape(-1).float() for d in data_list] + [t_host["tr"], t_host["rot"], t_host["tor"]]
+    # positions noised on the device (NoiseTransform.apply_noise_batch) do not go through the host staging buffer: see below
+    pos_on_dev = any(d["ligand"].pos.is_cuda for d in data_list)
+    fparts = ([] if pos_on_dev else [d["ligand"].pos.reshape(-1).float() for d in data_list]) + [t_host["tr"], t_host["rot"], t_host["tor"]]
     iparts = [torch.from_numpy(a) for a in (np.repeat(np.arange(len(nl)), nl), np.repeat(np.arange(len(nr)), nr), rot,
                                             np.repeat(np.asarray(lo, dtype=np.int64), ne_l), np.repeat(np.asarray(ro, dtype=np.int64), ne_r),
                                             np.concatenate([[0], np.cumsum(nl)]).astype(np.int64), np.concatenate([[0], np.cumsum(nr)]).astype(np.int64))]
@@ -94,7 +96,7 @@ def collate(data_list: List[HeteroData], device, keep=None) -> Batch:
         return out, dev_t
 
     (fdev, fall), (idev, _) = stage(fparts, torch.float32), stage(iparts, torch.int64)
-    B = len(data_list)
+    B = 0 if pos_on_dev else len(data_list)      # index of the first time vector in fdev
 
     def edges(parts, per_edge_offset, role):
         """edge_index tensors: cached raw copies concatenated on the device, per-graph node offsets added with one op"""
@@ -105,7 +107,6 @@ def collate(data_list: List[HeteroData], device, keep=None) -> Batch:
         return out
 
     b["ligand"].x = dv([d["ligand"].x for d in data_list], static=True, role="lig_x")
-    b["ligand"].pos = fall[:3 * sum(nl)].view(-1, 3)
     b["ligand"].edge_mask = dv([d["ligand"].edge_mask for d in data_list], static=True, role="lig_edge_mask")
     b["ligand"].batch = idev[0]
     b["ligand", "ligand"].edge_index = edges([d["ligand", "ligand"].edge_index for d in data_list], idev[3], "lig_edge_index")
@@ -121,6 +122,16 @@ def collate(data_list: List[HeteroData], device, keep=None) -> Batch:
     # read the count back)
     b.rot_bond_cols = idev[2]
     b.lig_ptr, b.rec_ptr = idev[5], idev[6]        # node offsets of the graphs: the batched radius searches scan [ptr[b], ptr[b + 1])
+    if pos_on_dev:
+        # concatenated on the side stream behind whatever produced them on the current one; last, so that the
+        # uploads above do not wait for it; an item left on the host (over the noise kernel's capacity) is uploaded on its own
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            lig_pos = torch.cat([d["ligand"].pos.float().to(device, non_blocking=True).reshape(-1, 3) for d in data_list])
+        keep_alive.append(lig_pos)
+        b["ligand"].pos = lig_pos
+    else:
+        b["ligand"].pos = fall[:3 * sum(nl)].view(-1, 3)
     if keep is None:            # stand-alone use: the compute stream waits here; prepare_batch() hands an event to forward() instead
         torch.cuda.current_stream(device).wait_stream(side)
         _keep_until_main_passes(keep_alive, device)

@@ -239,6 +239,23 @@ int cbd_match_torsions(int32_t n_problems, int32_t max_nl, int32_t max_r, const 
                        uint64_t seed, int32_t popsize, int32_t maxiter, float mutation_lo, float mutation_hi, float recombination, float tol,
                        float* theta_out_dev, float* fitness_out_dev, int32_t* generations_out_dev, void* stream);
 
+/* Forward-diffusion move of a whole fine-tuning batch: the pose arithmetic of NoiseTransform.apply_noise (reference
+ * datasets/pdbbind.py:60-110) -> modify_conformer (utils/diffusion_utils.py:33-58, pivot = None) for n_ligands DIFFERENT ligands in
+ * one launch, one wavefront each.  The random updates are drawn by the caller (host generators, reference order); per ligand p
+ *   rigid = (pos - centroid) Rm^T + tr[p] + centroid, Rm = rotation of the axis-angle vector rot[p] (quaternion route, with the
+ *   |angle| < 1e-6 series branch); then for bond r in order, unless tor[r] == 0, the atoms of mask_rotate[r] turn by tor[r] about
+ *   pos[u_r] - pos[v_r] through pos[v_r]; the result is Kabsch-aligned onto `rigid`.  R = 0, or tor_dev = NULL (no_torsion): pos_out = rigid.
+ * Ragged layout, prefix sums over the ligands: lig_ptr [n + 1] atoms (pos_in / pos_out [sum Nl][3]); rot_ptr [n + 1] rotatable bonds
+ * (rot_edge [sum R][2] = LOCAL atom indices (u, v) in the ligand's edge_mask order, tor [sum R]); mask_ptr [n + 1] 32-bit words of
+ * mask_bits, which holds per ligand mask_rotate [R][ceil(Nl / 32)] with atom a at bit a % 32 of word a / 32.  tr, rot [n][3].
+ * max_nl / max_r: the largest Nl / R of the launch.  Capacity Nl <= 512, R <= 128: larger values return CBD_ERR_CAPACITY and nothing
+ * is launched or written (never truncated).  A ligand whose own sizes exceed max_nl / max_r is left unwritten, one with a bond end
+ * outside [0, Nl) gets NaN; neither reads out of bounds.  No atomics: bitwise repeatable, and a ligand's result does not depend on
+ * what shares the launch.  Device pointers; asynchronous on `stream`. */
+int cbd_noise_conformers(int32_t n_ligands, int32_t max_nl, int32_t max_r, const int32_t* lig_ptr_dev, const float* pos_in_dev,
+                         const int32_t* rot_ptr_dev, const int32_t* rot_edge_dev, const int32_t* mask_ptr_dev, const uint32_t* mask_bits_dev,
+                         const float* tr_dev, const float* rot_dev, const float* tor_dev, float* pos_out_dev, void* stream);
+
 /* ============================ all-atom CONFIDENCE model ===========================================
  * Replaces, for the shipped workdir/pretrained_confidence architecture, the confidence branch of
  * utils/sampling.py:240-261: crop_beyond (utils/utils.py:395-420) + set_time(0) + the all-atom
