@@ -17,13 +17,14 @@ import torch
 
 from .engine import DockEngine, make_steps
 from .hetero import Batch
-from .sampling import randomize_position
+from .sampling import randomize_position, randomize_position_batch
 
 
 class ComplexSetRunner:
     """Engines (one score engine + `group - 1` partners sharing its weights, one confidence engine) and the per-group work."""
 
-    def __init__(self, score_model, score_args, conf_model, conf_args, device, samples=40, denoise_steps=20, group=4, keep_poses=False):
+    def __init__(self, score_model, score_args, conf_model, conf_args, device, samples=40, denoise_steps=20, group=4, keep_poses=False,
+                 device_randomize=False):
         from .diffusion_utils import get_t_schedule
         self.dev = torch.device(device)
         self.samples, self.S, self.group = int(samples), int(denoise_steps), max(1, min(int(group), 8))
@@ -52,6 +53,7 @@ class ComplexSetRunner:
         # one confidence engine per complex of a group: up to four complexes are scored in ONE set of fused-conv launches
         self.cengs = ([self.ceng] + conf_model.co_engines(min(self.group, 4) - 1, self.ceng)) if conf_model is not None else []
         self.keep_poses = keep_poses
+        self.device_randomize = bool(device_randomize)      # opt-in: a complex's starting poses in one cbd_randomize_poses launch
         self.times = {"setup": 0.0, "sample": 0.0, "conf": 0.0}
         self.prepared: Dict[int, tuple] = {}
 
@@ -67,7 +69,10 @@ class ComplexSetRunner:
             torch.manual_seed(i)
             np.random.seed(i)
             dl = [Batch.from_data_list([copy.deepcopy(cplx)]) for _ in range(self.samples)]
-            randomize_position(dl, False, False, self.score_args.tr_sigma_max)
+            if self.device_randomize:
+                randomize_position_batch([dl], False, False, self.score_args.tr_sigma_max, self.dev)
+            else:
+                randomize_position(dl, False, False, self.score_args.tr_sigma_max)
             pos0 = torch.stack([d["ligand"].pos for d in dl]).contiguous()
             R = int(cplx["ligand"].edge_mask.sum())
             noise = (torch.randn(self.S, self.samples, 3), torch.randn(self.S, self.samples, 3), torch.randn(self.S, self.samples * R))

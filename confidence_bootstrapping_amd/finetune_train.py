@@ -19,7 +19,7 @@ import torch
 from .diffusion_utils import get_inverse_schedule, get_t_schedule
 from .hetero import Batch
 from .molecules_utils import get_symmetry_rmsd, remove_all_hs
-from .sampling import randomize_position, sampling
+from .sampling import randomize_position, randomize_position_batch, sampling
 from .training import loss_function, train_epoch
 from .hostcfg import with_glue_threads
 
@@ -62,6 +62,8 @@ def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_di
         return [(preds[k * n:(k + 1) * n], None if conf is None else conf[k * n:(k + 1) * n]) for k in range(len(items))]
 
     prepared = []
+    device_randomize = bool(getattr(args, "device_randomize", False))
+    pocket = dict(pocket_knowledge=getattr(args, "inf_pocket_knowledge", False), pocket_cutoff=getattr(args, "inf_pocket_cutoff", 7))
     for orig in complex_graphs:
         orig = _as_batch1(orig)
         name = orig.name[0] if isinstance(orig.name, (list, tuple)) else orig.name
@@ -72,12 +74,15 @@ def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_di
                 continue
             filtering_data_list = [_copy(filtering_complex_dict[name]) for _ in range(n)]
         data_list = [_copy(orig) for _ in range(n)]
-        randomize_position(data_list, args.no_torsion, False, args.tr_sigma_max,
-                           pocket_knowledge=getattr(args, "inf_pocket_knowledge", False), pocket_cutoff=getattr(args, "inf_pocket_cutoff", 7))
+        if not device_randomize:
+            randomize_position(data_list, args.no_torsion, False, args.tr_sigma_max, **pocket)
         prepared.append((orig, data_list, filtering_data_list))
 
     results = []
     group = 8 if n % max(args.inference_batch_size, 1) == 0 else 1      # loader batches must not straddle complexes
+    if device_randomize:      # opt-in: the starting poses of each group of co-scheduled complexes in one launch, same draws in the same order
+        for k in range(0, len(prepared), group):
+            randomize_position_batch([it[1] for it in prepared[k:k + group]], args.no_torsion, False, args.tr_sigma_max, device, **pocket)
     for k in range(0, len(prepared), group):
         items = prepared[k:k + group]
         try:

@@ -62,9 +62,9 @@ def modify_conformer_torsion_angles(pos, edge_index, mask_rotate, torsion_update
     return pos if as_numpy else torch.from_numpy(pos.astype(np.float32))
 
 
-def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, pocket_knowledge=False, pocket_cutoff=7):
-    """In-place initial pose randomisation; RNG use identical to the reference (numpy global for torsions,
-    scipy Rotation.random, torch global for the translation)."""
+def _pocket_center(data_list, pocket_knowledge=False, pocket_cutoff=7):
+    """Where randomize_position puts the ligands of `data_list` (copies of one complex): the receptor's centroid, or with
+    `pocket_knowledge` the centroid of the residues within `pocket_cutoff` of the crystal pose (the nearest residue if there is none)."""
     center_pocket = data_list[0]["receptor"].pos.mean(dim=0)
     if pocket_knowledge:
         cg = data_list[0]
@@ -76,6 +76,13 @@ def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, pocket_kn
             center_pocket = cg["receptor"].pos[label].mean(dim=0)
         else:
             center_pocket = cg["receptor"].pos[torch.argmin(torch.min(d, dim=1)[0])]
+    return center_pocket
+
+
+def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, pocket_knowledge=False, pocket_cutoff=7):
+    """In-place initial pose randomisation; RNG use identical to the reference (numpy global for torsions,
+    scipy Rotation.random, torch global for the translation)."""
+    center_pocket = _pocket_center(data_list, pocket_knowledge, pocket_cutoff)
     if not no_torsion:
         for g in data_list:
             n_tor = int(g["ligand"].edge_mask.sum())
@@ -88,6 +95,139 @@ def randomize_position(data_list, no_torsion, no_random, tr_sigma_max, pocket_kn
         g["ligand"].pos = (g["ligand"].pos - molecule_center) @ random_rotation.T + center_pocket
         if not no_random:
             g["ligand"].pos += torch.normal(mean=0, std=tr_sigma_max, size=(1, 3))
+
+
+def draw_randomization(data_list, no_torsion, no_random, tr_sigma_max):
+    """The draws of randomize_position(data_list, ...) without moving a pose, from the same global generators in the same order and
+    sizes: every pose's torsion updates first, then a rotation per pose (both on numpy's global generator), then a translation per
+    pose (torch's): afterwards both generators are where randomize_position leaves them.
+    -> (tor: list of float64 [R] per pose, or None with no_torsion; rot_mat: float32 tensor [n, 3, 3], scipy's matrices cast the way
+    randomize_position casts them; tr: float32 tensor [n, 1, 3], or None with no_random)"""
+    tor = None
+    if not no_torsion:
+        tor = [np.random.uniform(low=-np.pi, high=np.pi, size=int(g["ligand"].edge_mask.sum())) for g in data_list]
+    rot_mat = torch.stack([torch.from_numpy(R.random().as_matrix()).float() for _ in data_list]) if len(data_list) else torch.zeros(0, 3, 3)
+    tr = None
+    if not no_random:
+        tr = torch.stack([torch.normal(mean=0, std=tr_sigma_max, size=(1, 3)) for _ in data_list]) if len(data_list) else torch.zeros(0, 1, 3)
+    return tor, rot_mat, tr
+
+
+def _randomize_with_draws(data_list, center_pocket, tor, rot_mat, tr):
+    """randomize_position's arithmetic, statement for statement, with the draws of draw_randomization prescribed: the host route of
+    randomize_position_batch for a complex over the kernel's capacity, and the host yardstick of tests/test_gpu_randomize_batch.py."""
+    if tor is not None:
+        for g, torsion_updates in zip(data_list, tor):
+            g["ligand"].pos = modify_conformer_torsion_angles(
+                g["ligand"].pos, g["ligand", "ligand"].edge_index.T[g["ligand"].edge_mask], _mask_rotate_of(g), torsion_updates)
+    for k, g in enumerate(data_list):
+        molecule_center = torch.mean(g["ligand"].pos, dim=0, keepdim=True)
+        g["ligand"].pos = (g["ligand"].pos - molecule_center) @ rot_mat[k].T + center_pocket
+        if tr is not None:
+            g["ligand"].pos += tr[k]
+
+
+RANDOMIZE_MAX_ATOMS, RANDOMIZE_MAX_TORSIONS = 512, 128      # capacity of cbd_randomize_poses per ligand (include/cbdock.h)
+
+
+def _same_ligand(a, b):
+    """do two graphs share start coordinates and torsion description (the copies of one complex do), so that one description serves both"""
+    la, lb = a["ligand"], b["ligand"]
+    ea, eb = a["ligand", "ligand"].edge_index, b["ligand", "ligand"].edge_index
+    ma, mb = _mask_rotate_of(a), _mask_rotate_of(b)
+    same = lambda x, y: x is y or (x.shape == y.shape and x.dtype == y.dtype and bool(torch.equal(x, y)))
+    return (same(la.pos, lb.pos) and same(ea, eb) and same(la.edge_mask, lb.edge_mask)
+            and (ma is mb or (ma.shape == mb.shape and np.array_equal(ma, mb))))
+
+
+def _pack_randomization(groups, centers, draws):
+    """The ragged batch cbd_randomize_poses reads, as host arrays.  `groups`: data_lists, one per complex (all within the capacity);
+    `centers`: their pocket centres; `draws`: their draw_randomization results.  The graphs of a group that share start coordinates and
+    torsion description (`_same_ligand` with the group's first graph) point at ONE ligand description, every other graph gets its own.
+    -> dict: pose_lig, pose_cplx [P]; out_ptr, tor_ptr [P + 1]; lig_ptr, rot_ptr, mask_ptr [L + 1] (int32); rot_edge int32 [sum R, 2];
+    mask_bits uint32 (flat); pos_in float32 [sum Nl, 3]; tor float64 [sum R over poses] or None; rot_mat float32 [P, 9]; tr float32
+    [P, 3] or None; center float32 [C, 3]; max_nl, max_r."""
+    from .datasets.pdbbind import pack_ligand
+    pose_lig, pose_cplx, nl_of, r_of, descs = [], [], [], [], []
+    for c, group in enumerate(groups):
+        first = len(descs)                   # the description of the group's first graph
+        for k, g in enumerate(group):
+            lig = first
+            if k == 0 or not _same_ligand(group[0], g):
+                lig = len(descs)
+                edges, bits = pack_ligand(g)
+                descs.append((g["ligand"].pos.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1, 3), edges, bits))
+            pose_lig.append(lig)
+            pose_cplx.append(c)
+            nl_of.append(descs[lig][0].shape[0])
+            r_of.append(descs[lig][1].shape[0])
+    ptr = lambda sizes: np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int32)
+
+    def cat(arrays, dtype, shape):
+        arrays = [np.asarray(a, dtype=dtype).reshape(shape) for a in arrays]
+        return np.concatenate(arrays) if arrays else np.zeros(tuple(0 if s == -1 else s for s in shape), dtype=dtype)
+    with_tor = bool(draws) and draws[0][0] is not None
+    with_tr = bool(draws) and draws[0][2] is not None
+    return dict(
+        pose_lig=np.asarray(pose_lig, dtype=np.int32), pose_cplx=np.asarray(pose_cplx, dtype=np.int32), out_ptr=ptr(nl_of), tor_ptr=ptr(r_of),
+        lig_ptr=ptr([d[0].shape[0] for d in descs]), rot_ptr=ptr([d[1].shape[0] for d in descs]), mask_ptr=ptr([d[2].size for d in descs]),
+        rot_edge=cat([d[1] for d in descs], np.int32, (-1, 2)), mask_bits=cat([d[2] for d in descs], np.uint32, (-1,)),
+        pos_in=cat([d[0] for d in descs], np.float32, (-1, 3)),
+        tor=cat([t for d in draws for t in d[0]], np.float64, (-1,)) if with_tor else None,
+        rot_mat=cat([d[1].numpy() for d in draws], np.float32, (-1, 9)),
+        tr=cat([d[2].numpy() for d in draws], np.float32, (-1, 3)) if with_tr else None,
+        center=cat([np.asarray(c) for c in centers], np.float32, (-1, 3)),
+        max_nl=max(nl_of, default=0), max_r=max(r_of, default=0))
+
+
+def randomize_position_batch(groups, no_torsion, no_random, tr_sigma_max, device, pocket_knowledge=False, pocket_cutoff=7):
+    """randomize_position for the data_lists of several complexes (`groups`: one data_list per complex) with the poses moved on the
+    GPU: draws per group in list order (draw_randomization: the generators advance as under randomize_position group after group),
+    ONE upload of the packed ragged batch, ONE cbd_randomize_poses launch on the current stream, ONE download; every graph's
+    `['ligand'].pos` is then an fp32 CPU tensor of its old shape.  A group with a ligand over the kernel's capacity (Nl > 512 or
+    R > 128) is moved on the host with the draws already made.  There is no CPU path: `device` must be a GPU.  No reference counterpart."""
+    import ctypes as C
+    from . import engine
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("randomize_position_batch moves the poses on the MI355X (cbd_randomize_poses); use randomize_position on the host")
+    lib = engine.load_library()
+    fit, centers, draws = [], [], []
+    for group in groups:
+        center = _pocket_center(group, pocket_knowledge, pocket_cutoff)
+        drawn = draw_randomization(group, no_torsion, no_random, tr_sigma_max)
+        if any(int(g["ligand"].pos.shape[0]) > RANDOMIZE_MAX_ATOMS or int(g["ligand"].edge_mask.sum()) > RANDOMIZE_MAX_TORSIONS for g in group):
+            _randomize_with_draws(group, center, *drawn)
+            continue
+        fit.append(group)
+        centers.append(center)
+        draws.append(drawn)
+    if not fit:
+        return groups
+    pk = _pack_randomization(fit, centers, draws)
+    # one staging buffer of 4-byte words; the fp64 torsion updates come first, so that they are 8-byte aligned on both sides
+    names = ("tor", "pose_lig", "pose_cplx", "out_ptr", "tor_ptr", "lig_ptr", "rot_ptr", "mask_ptr", "rot_edge", "mask_bits", "pos_in",
+             "rot_mat", "tr", "center")
+    parts = [(np.zeros(0, np.int32) if pk[k] is None else np.ascontiguousarray(pk[k]).reshape(-1).view(np.int32)) for k in names]
+    offs = dict(zip(names, np.concatenate([[0], np.cumsum([len(p) for p in parts])[:-1]])))
+    host = torch.empty(sum(len(p) for p in parts), dtype=torch.int32, pin_memory=True)
+    np.concatenate(parts, out=host.numpy())
+    n_atoms = int(pk["out_ptr"][-1])
+    with torch.cuda.device(dev):
+        staged = host.to(dev, non_blocking=True)
+        out = torch.empty(n_atoms, 3, dtype=torch.float32, device=dev)
+        at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k])) if pk[k] is not None and pk[k].size else None    # NULL when empty
+        rc = lib.cbd_randomize_poses(len(pk["pose_lig"]), len(pk["lig_ptr"]) - 1, len(fit), int(pk["max_nl"]), int(pk["max_r"]),
+                                     at("pose_lig"), at("pose_cplx"), at("out_ptr"), at("tor_ptr"), at("lig_ptr"), at("pos_in"),
+                                     at("rot_ptr"), at("rot_edge"), at("mask_ptr"), at("mask_bits"), at("tor"), at("rot_mat"), at("tr"),
+                                     at("center"), C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
+        moved = out.cpu()      # the one download; it also orders `staged` and `host` behind the kernel
+    graphs = [g for group in fit for g in group]
+    for g, a0, a1 in zip(graphs, pk["out_ptr"][:-1], pk["out_ptr"][1:]):
+        g["ligand"].pos = moved[int(a0):int(a1)].clone()
+    return groups
 
 
 def _draw_chunk_noise(b, R_, S, no_final_step_noise=False):

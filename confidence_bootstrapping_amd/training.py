@@ -515,7 +515,7 @@ def inference_epoch_fix(model, complex_graphs, device, t_to_sigma, args):
     from .diffusion_utils import get_inverse_schedule, get_t_schedule
     from .hetero import Batch
     from .molecules_utils import get_symmetry_rmsd, remove_all_hs
-    from .sampling import randomize_position, sampling
+    from .sampling import randomize_position, randomize_position_batch, sampling
     t_schedule = get_t_schedule(sigma_schedule="expbeta", inference_steps=args.inference_steps, inf_sched_alpha=1, inf_sched_beta=1)
     asyn = bool(getattr(args, "asyncronous_noise_schedule", False))
     if asyn:
@@ -530,8 +530,11 @@ def inference_epoch_fix(model, complex_graphs, device, t_to_sigma, args):
     for orig in complex_graphs:
         orig = orig if isinstance(orig, Batch) else Batch.from_data_list([orig])
         data_list = [orig.shallow_copy() if hasattr(orig, "shallow_copy") else copy.deepcopy(orig) for _ in range(args.inference_samples)]
-        randomize_position(data_list, args.no_torsion, False, args.tr_sigma_max, pocket_knowledge=getattr(args, "inf_pocket_knowledge", False),
-                           pocket_cutoff=getattr(args, "inf_pocket_cutoff", 7))
+        pocket = dict(pocket_knowledge=getattr(args, "inf_pocket_knowledge", False), pocket_cutoff=getattr(args, "inf_pocket_cutoff", 7))
+        if getattr(args, "device_randomize", False):      # opt-in: the complex's starting poses in one launch, same draws in the same order
+            randomize_position_batch([data_list], args.no_torsion, False, args.tr_sigma_max, device, **pocket)
+        else:
+            randomize_position(data_list, args.no_torsion, False, args.tr_sigma_max, **pocket)
         predictions_list, failed = None, 0
         while predictions_list is None and failed <= 5:
             try:

@@ -256,6 +256,31 @@ int cbd_noise_conformers(int32_t n_ligands, int32_t max_nl, int32_t max_r, const
                          const int32_t* rot_ptr_dev, const int32_t* rot_edge_dev, const int32_t* mask_ptr_dev, const uint32_t* mask_bits_dev,
                          const float* tr_dev, const float* rot_dev, const float* tor_dev, float* pos_out_dev, void* stream);
 
+/* Starting poses of an inference epoch: the pose arithmetic of randomize_position (reference utils/sampling.py:15-48) for n_poses
+ * poses of n_complexes complexes in one launch, one wavefront each.  The random draws are made by the caller (host generators,
+ * reference order); per pose p, with l = pose_lig[p]:
+ *   flex = pos_in of ligand l; for bond r in order, unless tor[r] == 0, the atoms of mask_rotate[r] turn by tor[r] about
+ *   flex[u_r] - flex[v_r] through flex[v_r] (no alignment afterwards); pos_out = (flex - mean(flex)) Rm^T + center[pose_cplx[p]] + tr[p]
+ *   with Rm = rot_mat[p] GIVEN as a row-major 3x3 matrix.  tor_dev = NULL (no_torsion): no bond turns; tr_dev = NULL (no_random): no tr.
+ * Ligand descriptions, prefix sums over the n_ligands ligands, the layout of cbd_noise_conformers: lig_ptr [L + 1] atoms (pos_in
+ * [sum Nl][3]); rot_ptr [L + 1] rotatable bonds (rot_edge [sum R][2] = LOCAL atom indices (u, v) in edge_mask order); mask_ptr [L + 1]
+ * 32-bit words of mask_bits = per ligand mask_rotate [R][ceil(Nl / 32)], atom a at bit a % 32 of word a / 32.  Poses: pose_lig,
+ * pose_cplx [P]; out_ptr [P + 1] atoms of pos_out and tor_ptr [P + 1] entries of tor, prefix sums over the poses of their ligands' Nl
+ * and R (tor is fp64, as the host draws it); rot_mat [P][9]; tr [P][3]; center [n_complexes][3].  rot_ptr, rot_edge, mask_ptr, mask_bits and tor_ptr may be NULL when
+ * tor_dev is NULL or max_r = 0.
+ * max_nl / max_r: the largest Nl / R of the launch.  Capacity Nl <= 512, R <= 128: larger values return CBD_ERR_CAPACITY and nothing
+ * is launched or written (never truncated).  A pose whose sizes exceed max_nl / max_r is left unwritten; one whose pose_lig /
+ * pose_cplx names no ligand / complex, whose out_ptr / tor_ptr extents differ from its ligand's Nl / R, whose ligand's lig_ptr /
+ * rot_ptr / mask_ptr entries are negative or decreasing, or whose ligand has a bond end
+ * outside [0, Nl) gets NaN: the kernel indexes with none of these before it has checked it (the lengths of the ragged arrays
+ * themselves are the caller's: the kernel cannot know them).  No atomics: bitwise repeatable, and a pose's result does not depend on what
+ * shares the launch.  n_poses = 0 returns 0 without a launch.  Device pointers; asynchronous on `stream`. */
+int cbd_randomize_poses(int32_t n_poses, int32_t n_ligands, int32_t n_complexes, int32_t max_nl, int32_t max_r,
+                        const int32_t* pose_lig_dev, const int32_t* pose_cplx_dev, const int32_t* out_ptr_dev, const int32_t* tor_ptr_dev,
+                        const int32_t* lig_ptr_dev, const float* pos_in_dev, const int32_t* rot_ptr_dev, const int32_t* rot_edge_dev,
+                        const int32_t* mask_ptr_dev, const uint32_t* mask_bits_dev, const double* tor_dev, const float* rot_mat_dev,
+                        const float* tr_dev, const float* center_dev, float* pos_out_dev, void* stream);
+
 /* ============================ all-atom CONFIDENCE model ===========================================
  * Replaces, for the shipped workdir/pretrained_confidence architecture, the confidence branch of
  * utils/sampling.py:240-261: crop_beyond (utils/utils.py:395-420) + set_time(0) + the all-atom

@@ -2,7 +2,7 @@
 defaults for the loop shape (README.md:52 of the reference: 8 samples per complex, inference batch 4, training batch 5,
 max_complexes_per_couple 20, EMA, 20 denoising steps) on a synthetic cluster of C2-sized complexes:
 
-    python tools/cb_loop.py [--complexes 12] [--epochs 3] [--cb-inference-freq 1] [--device-noise]
+    python tools/cb_loop.py [--complexes 12] [--epochs 3] [--cb-inference-freq 1] [--device-noise] [--device-randomize]
 
 Prints per-epoch logs and one JSON line with the time split (sampling + confidence + RMSD / training) and the rates."""
 import argparse
@@ -22,10 +22,10 @@ sys.path.insert(0, ROOT)
 
 
 def run(complexes=12, epochs=3, cb_inference_freq=1, samples=8, steps=20, workload="c2_dockgen_median", host_threads=16, quiet=False,
-        device_noise=False):
+        device_noise=False, device_randomize=False):
     """-> dict with the time split of the loop (bench.py's `cb_round` leg calls this with the reference's loop shape)"""
     a = Namespace(complexes=complexes, epochs=epochs, cb_inference_freq=cb_inference_freq, samples=samples, steps=steps, workload=workload,
-                  host_threads=host_threads, device_noise=device_noise)
+                  host_threads=host_threads, device_noise=device_noise, device_randomize=device_randomize)
     threads_before = torch.get_num_threads()
     torch.set_num_threads(a.host_threads)
     try:
@@ -66,7 +66,8 @@ def _run(a, quiet):
     args.__dict__.update(inference_steps=a.steps, inference_samples=a.samples, inference_batch_size=4, n_epochs=a.epochs,
                          cb_inference_freq=a.cb_inference_freq, initial_iterations=1, inference_iterations=1,
                          num_inference_complexes=a.complexes, batch_size=5, use_ema=True, tr_weight=0.33, rot_weight=0.33, tor_weight=0.33,
-                         device_noise=a.device_noise)     # noise each training batch with one launch (NoiseTransform.apply_noise_batch)
+                         device_noise=a.device_noise,     # noise each training batch with one launch (NoiseTransform.apply_noise_batch)
+                         device_randomize=a.device_randomize)     # starting poses of each group of complexes with one launch (randomize_position_batch)
     t2s = partial(t_to_sigma, args=margs)
     buf = CBBuffer(cluster_name="c", cluster_to_ligands={"c": names}, max_complexes_per_couple=20,
                    transform=NoiseTransform(t_to_sigma=t2s, no_torsion=False, all_atom=False))
@@ -127,9 +128,11 @@ def main():
     ap.add_argument("--host-threads", type=int, default=16, help="intra-op threads of the host-side numpy/torch code (the reference's "
                     "--restrict_cpu uses 16, inference.py:225-234); tiny LAPACK/BLAS calls crawl on an unrestricted 128-thread pool")
     ap.add_argument("--device-noise", action="store_true", help="noise every training batch on the GPU in one launch (off by default)")
+    ap.add_argument("--device-randomize", action="store_true", help="randomise the starting poses of every group of complexes on the GPU "
+                    "in one launch (off by default)")
     a = ap.parse_args()
     print(json.dumps(run(a.complexes, a.epochs, a.cb_inference_freq, a.samples, a.steps, a.workload, a.host_threads,
-                         device_noise=a.device_noise)))
+                         device_noise=a.device_noise, device_randomize=a.device_randomize)))
 
 
 if __name__ == "__main__":

@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--samples", type=int, default=40)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--device-randomize", action="store_true", help="move each complex's starting poses on the GPU in one launch (off by default)")
     a = ap.parse_args()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -42,7 +43,8 @@ def main():
     sizes = complex_set_sizes(a.complexes, a.seed)          # log-normal around the median complex
     smodel, sargs = make_score_model(device=dev, seed=0)
     cmodel, cargs = make_confidence_model(device=dev, seed=5)
-    runner = ComplexSetRunner(smodel, sargs, cmodel, cargs, dev, samples=a.samples, denoise_steps=a.steps, group=4)
+    runner = ComplexSetRunner(smodel, sargs, cmodel, cargs, dev, samples=a.samples, denoise_steps=a.steps, group=4,
+                              device_randomize=a.device_randomize)
     # host-side synthesis of the complexes is data loading, outside the timed region (the LPT partition inside run_complex_set decides
     # which ones this rank samples; it only needs the sizes)
 
