@@ -35,6 +35,123 @@ def pose_metrics(ligand_pos, orig_ligand_pos, mol=None, device=None):
     return rmsd, centroid, d.flatten(1).min(dim=1).values.numpy()
 
 
+METRICS_MAX_ATOMS, METRICS_MAX_REF_ATOMS = 512, 4096      # capacity of cbd_pose_metrics per complex: N and Q * N (include/cbdock.h)
+
+
+def _prepare_metrics_items(items, isomorphisms=None):
+    """Host half of pose_metrics_batch, no GPU: per item the fp32 arrays, the sizes and the isomorphism cache entry.
+    `items`: (ligand_pos [P, N, 3], orig_pos [Q, N, 3] or [N, 3], mol or None); `isomorphisms`: optional list, one (idx1, idx2) or None per
+    item, used as given instead of the cache.  mol None, or an enumeration that raised: the identity mapping (K = 1), after the line the
+    host route prints.  -> list of dicts lp, ref, mol, P, N, Q, K, key, entry, fits."""
+    from . import molecules_utils as mu
+    out = []
+    for i, (ligand_pos, orig_pos, mol) in enumerate(items):
+        lp = np.ascontiguousarray(np.asarray(ligand_pos, dtype=np.float32))
+        ref = np.asarray(orig_pos, dtype=np.float32)
+        ref = np.ascontiguousarray(ref[None] if ref.ndim == 2 else ref)
+        if lp.ndim != 3 or lp.shape[2] != 3 or ref.ndim != 3 or ref.shape[0] < 1 or ref.shape[1:] != lp.shape[1:]:
+            raise ValueError(f"item {i}: poses {lp.shape} and crystal poses {ref.shape} do not match")
+        n = lp.shape[1]
+        given = isomorphisms[i] if isomorphisms is not None else None
+        key = entry = None
+        if given is not None:
+            idx1, idx2 = (np.ascontiguousarray(np.asarray(x, dtype=np.int32)) for x in given)
+            if idx1.ndim != 2 or idx1.shape != idx2.shape or idx1.shape[0] < 1 or idx1.shape[1] != n:
+                raise ValueError(f"item {i}: isomorphism tables {idx1.shape} / {idx2.shape} for {n} atoms")
+            entry = {"iso": (idx1, idx2), "exc": None, "dev": {}, "bytes": 0}
+        elif mol is not None:
+            try:
+                key, entry = mu._iso_entry(*mu._graph_of(mol))
+                if entry["exc"] is not None:
+                    raise entry["exc"][0](*entry["exc"][1])
+                if entry["iso"][0].shape[1] != n:
+                    raise ValueError("coordinate / isomorphism shapes do not match")
+            except Exception as e:
+                print("Using non corrected RMSD because of the error:", e)
+                key = entry = None
+        if entry is None:
+            key, entry = mu._identity_entry(n)
+        out.append(dict(lp=lp, ref=ref, mol=mol, P=lp.shape[0], N=n, Q=ref.shape[0], K=entry["iso"][0].shape[0], key=key, entry=entry,
+                        fits=1 <= n <= METRICS_MAX_ATOMS and ref.shape[0] * n <= METRICS_MAX_REF_ATOMS))
+    return out
+
+
+def _pack_pose_metrics(prepared):
+    """The ragged batch cbd_pose_metrics reads, as host arrays, for prepared items that fit the kernel; one complex per item, its poses
+    in order.  -> dict: pose_cplx [P], pose_ptr [P + 1], cplx_n, cplx_k, cplx_q [C], ref_ptr [C + 1] (int32; the ptr arrays count
+    atoms), pos float32 [sum N over poses, 3], ref float32 [sum Q N, 3], idx_ref / idx_pos (lists of the C host tables [K, N]), max_n,
+    max_ref."""
+    ptr = lambda sizes: np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int32)
+    cat = lambda arrays: np.concatenate([a.reshape(-1, 3) for a in arrays]) if arrays else np.zeros((0, 3), dtype=np.float32)
+    return dict(
+        pose_cplx=np.asarray([c for c, it in enumerate(prepared) for _ in range(it["P"])], dtype=np.int32),
+        pose_ptr=ptr([it["N"] for it in prepared for _ in range(it["P"])]),
+        cplx_n=np.asarray([it["N"] for it in prepared], dtype=np.int32), cplx_k=np.asarray([it["K"] for it in prepared], dtype=np.int32),
+        cplx_q=np.asarray([it["Q"] for it in prepared], dtype=np.int32), ref_ptr=ptr([it["Q"] * it["N"] for it in prepared]),
+        pos=cat([it["lp"] for it in prepared]), ref=cat([it["ref"] for it in prepared]),
+        idx_ref=[it["entry"]["iso"][0] for it in prepared], idx_pos=[it["entry"]["iso"][1] for it in prepared],
+        max_n=max((it["N"] for it in prepared), default=0), max_ref=max((it["Q"] * it["N"] for it in prepared), default=0))
+
+
+def _pose_metrics_host(it, device):
+    """an item over the kernel's capacity on the existing host route; that route does not report which crystal pose / isomorphism won (-1)"""
+    rmsd, centroid, min_self = pose_metrics(it["lp"], it["ref"], it["mol"], device=device)
+    none = np.full(it["P"], -1, dtype=np.int32)
+    return (np.asarray(rmsd, dtype=np.float32), np.asarray(centroid, dtype=np.float32), np.asarray(min_self, dtype=np.float32), none, none.copy())
+
+
+def pose_metrics_batch(items, device, isomorphisms=None):
+    """pose_metrics for the poses of several complexes at once.  `items`: list of (ligand_pos [P, N, 3], orig_pos [Q, N, 3] or [N, 3],
+    mol or None), heavy atoms, same frame.  -> per item (rmsd, centroid, min_self, argmin_ref, argmin_iso): float32 / int32 arrays [P].
+    The isomorphisms come from the process-wide cache (molecules_utils.cached_isomorphisms' entries) and their index tables stay on the
+    device between calls, in the same LRU; everything else goes into ONE pinned staging buffer: ONE upload, ONE cbd_pose_metrics launch
+    on the current stream, ONE download.  rmsd is bitwise what get_symmetry_rmsd per crystal pose followed by np.min gives.  mol None, or
+    a ligand whose enumeration raised: the identity mapping (K = 1, fp64 sums -- the host route's fp32 numpy fall-back can differ from it
+    in the last bit).  An item over the kernel's capacity (N > 512 or Q * N > 4096) takes the host route (pose_metrics).  `isomorphisms`:
+    optional list with one (idx1, idx2) or None per item, used as given (not cached).  There is no CPU path: `device` must be a GPU."""
+    import ctypes as C
+    from . import engine, molecules_utils as mu
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pose_metrics_batch measures the poses on the MI355X (cbd_pose_metrics); use pose_metrics on the host")
+    lib = engine.load_library()
+    prepared = _prepare_metrics_items(items, isomorphisms)
+    empty = lambda: (np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    results = [None if it["fits"] and it["P"] else (_pose_metrics_host(it, dev) if it["P"] else empty()) for it in prepared]
+    fit = [it for it, r in zip(prepared, results) if r is None]
+    if not fit:
+        return results
+    pk = _pack_pose_metrics(fit)
+    n_poses = len(pk["pose_cplx"])
+    with torch.cuda.device(dev):
+        tables = [mu._iso_device_tables(it["key"], it["entry"], dev) for it in fit]      # resident; uploaded only when first seen
+        pk["idx_ref_tab"] = np.asarray([t[0].data_ptr() for t in tables], dtype=np.uint64)
+        pk["idx_pos_tab"] = np.asarray([t[1].data_ptr() for t in tables], dtype=np.uint64)
+        # one staging buffer of 4-byte words; the 8-byte pointer tables come first, so that they are aligned on both sides
+        names = ("idx_ref_tab", "idx_pos_tab", "pose_cplx", "pose_ptr", "cplx_n", "cplx_k", "cplx_q", "ref_ptr", "pos", "ref")
+        parts = [np.ascontiguousarray(pk[k]).reshape(-1).view(np.int32) for k in names]
+        offs = dict(zip(names, np.concatenate([[0], np.cumsum([len(p) for p in parts])[:-1]])))
+        host = torch.empty(sum(len(p) for p in parts), dtype=torch.int32, pin_memory=True)
+        np.concatenate(parts, out=host.numpy())
+        staged = host.to(dev, non_blocking=True)
+        out = torch.empty(5, n_poses, dtype=torch.int32, device=dev)      # rmsd, centroid, min_self (fp32 bits), argmin_ref, argmin_iso
+        at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k]))
+        row = lambda r: C.c_void_p(out.data_ptr() + 4 * r * n_poses)
+        rc = lib.cbd_pose_metrics(n_poses, len(fit), int(pk["max_n"]), int(pk["max_ref"]), at("pose_cplx"), at("pose_ptr"), at("pos"),
+                                  at("cplx_n"), at("cplx_k"), at("cplx_q"), at("ref_ptr"), at("ref"), at("idx_ref_tab"), at("idx_pos_tab"),
+                                  row(0), row(1), row(2), row(3), row(4), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
+        got = out.cpu().numpy()      # the one download; it also orders `staged`, `host` and the index tables behind the kernel
+    f32, p0 = got[:3].view(np.float32), 0
+    fit_ids = [i for i, r in enumerate(results) if r is None]
+    for i, it in zip(fit_ids, fit):
+        p1 = p0 + it["P"]
+        results[i] = (f32[0, p0:p1].copy(), f32[1, p0:p1].copy(), f32[2, p0:p1].copy(), got[3, p0:p1].copy(), got[4, p0:p1].copy())
+        p0 = p1
+    return results
+
+
 def _block(prefix, rmsd, centroid, self_dist=None):
     """the reference's standard group of entries for one selection of poses (one value per complex)"""
     pct = lambda a, thr: (100 * (a < thr).sum() / len(a)).__round__(2)

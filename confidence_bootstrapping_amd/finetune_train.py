@@ -34,6 +34,80 @@ def _as_batch1(g):
     return g if isinstance(g, Batch) else Batch.from_data_list([g])
 
 
+def _crystal_inputs(orig, predictions_list, ligand_pos):
+    """What the RMSD of a complex's poses is measured on: (heavy-atom poses [P, N, 3], crystal poses [Q, N, 3] in the frame of the poses,
+    heavy-atom graph or None); None when the crystal pose is not known."""
+    orig_pos = getattr(orig["ligand"], "orig_pos", None)
+    if orig_pos is None:
+        return None
+    if isinstance(orig_pos, list):
+        orig_pos = orig_pos[0]
+    orig_pos = np.asarray(orig_pos, dtype=np.float32)
+    orig_pos = orig_pos[None] if orig_pos.ndim == 2 else orig_pos
+    filterHs = torch.not_equal(predictions_list[0]["ligand"].x[:, 0], 0).cpu().numpy()
+    lp = ligand_pos[:, filterHs]
+    ref = orig_pos[:, filterHs] - orig.original_center.cpu().numpy()
+    mol = getattr(orig, "mol", None)
+    mol = mol[0] if isinstance(mol, (list, tuple)) else mol
+    mol = remove_all_hs(mol)          # RemoveAllHs(orig_complex_graph.mol[0]) in the reference; the coordinates are filtered with filterHs
+    return lp, ref, mol
+
+
+def summarize_inference(results, args, filtering_args, confidence_cutoff, device, group=1):
+    """The post-processing of inference_epoch (reference finetune_train.py:198-245): `results` = [((orig, data_list, filtering_data_list),
+    (predictions_list, confidences)), ...] in sampling order -> (losses, [(graph, confidence), ...] above the cutoff, top-confidence
+    RMSDs).  With `args.device_metrics` (opt-in) the RMSDs of each `group` consecutive complexes come from one
+    evaluation.pose_metrics_batch call (cached isomorphisms, one upload / launch / download) instead of one get_symmetry_rmsd call per
+    complex and crystal pose; everything else, and the order of every list, is the same."""
+    rmsds, min_rmsds, top_rmsds, confidences_list, complexes_to_keep = [], [], [], [], []
+    positions = [np.asarray([g["ligand"].pos.cpu().numpy() for g in predictions_list]) for _, (predictions_list, _) in results]
+    inputs = [_crystal_inputs(orig, predictions_list, ligand_pos)
+              for ((orig, _, _), (predictions_list, _)), ligand_pos in zip(results, positions)]
+    device_rmsd = {}
+    if getattr(args, "device_metrics", False):
+        from .evaluation import pose_metrics_batch
+        for k in range(0, len(results), max(int(group), 1)):
+            ids = [i for i in range(k, min(k + max(int(group), 1), len(results))) if inputs[i] is not None]
+            if ids:
+                for i, out in zip(ids, pose_metrics_batch([inputs[i] for i in ids], device)):
+                    device_rmsd[i] = out[0].astype(np.float64)
+    for i, ((orig, _, _), (predictions_list, confidences)) in enumerate(results):
+        if confidences is not None and isinstance(getattr(filtering_args, "rmsd_classification_cutoff", None), list):
+            confidences = confidences[:, 0]
+        if inputs[i] is not None:   # crystal pose known: RMSD metrics
+            lp, ref, mol = inputs[i]
+            if i in device_rmsd:
+                rmsd = device_rmsd[i]
+            else:
+                per_ref = []
+                for r in ref:
+                    try:
+                        per_ref.append(np.asarray(get_symmetry_rmsd(mol, r, [l for l in lp], device=device)))
+                    except Exception as e:
+                        print("Using non corrected RMSD because of the error:", e)
+                        per_ref.append(np.sqrt(((lp - r) ** 2).sum(axis=2).mean(axis=1)))
+                rmsd = np.min(np.asarray(per_ref), axis=0)
+            rmsds.extend(rmsd.tolist())
+            min_rmsds.append(rmsd.min())
+            if confidences is not None:
+                top_rmsds.append(rmsd[int(np.argmax(np.asarray([float(c) for c in confidences])))])
+            if getattr(args, "oracle_confidence", False):
+                confidences = -4 * np.tanh(2 * rmsd / 3 - 2)
+        if confidences is None:
+            continue
+        confidences_list.extend(float(c) for c in confidences)
+        complexes_to_keep.extend((predictions_list[i_], float(confidences[i_])) for i_ in range(len(predictions_list))
+                                 if float(confidences[i_]) > confidence_cutoff)
+    rmsds, min_rmsds, top_rmsds, conf = (np.asarray(x, dtype=np.float64) for x in (rmsds, min_rmsds, top_rmsds, confidences_list))
+    pct = lambda a, thr, n: float(100 * (a < thr).sum() / n) if n else None
+    losses = {"rmsds_lt2": pct(rmsds, 2, len(rmsds)), "rmsds_lt5": pct(rmsds, 5, len(rmsds)),
+              "filtered_rmsds_lt2": pct(top_rmsds, 2, len(min_rmsds)), "filtered_rmsds_lt5": pct(top_rmsds, 5, len(min_rmsds)),
+              "min_rmsds_lt2": pct(min_rmsds, 2, len(min_rmsds)), "min_rmsds_lt5": pct(min_rmsds, 5, len(min_rmsds)),
+              "avg_confidence": float(conf.mean()) if len(conf) else None,
+              "median_confidence": float(np.median(conf)) if len(conf) else None}
+    return losses, complexes_to_keep, top_rmsds
+
+
 @with_glue_threads
 def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_dict, device, t_to_sigma, args, filtering_args,
                     confidence_cutoff):
@@ -47,7 +121,6 @@ def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_di
         tor_schedule = get_inverse_schedule(t_schedule, args.tor_alpha, args.tor_beta)
     else:
         tr_schedule = rot_schedule = tor_schedule = t_schedule
-    rmsds, min_rmsds, top_rmsds, confidences_list, complexes_to_keep = [], [], [], [], []
     model.eval()
     n = args.inference_samples
 
@@ -105,49 +178,7 @@ def inference_epoch(model, filtering_model, complex_graphs, filtering_complex_di
                 continue
             results.append((it, out))
 
-    for (orig, _, _), (predictions_list, confidences) in results:
-        ligand_pos = np.asarray([g["ligand"].pos.cpu().numpy() for g in predictions_list])
-        if confidences is not None and isinstance(getattr(filtering_args, "rmsd_classification_cutoff", None), list):
-            confidences = confidences[:, 0]
-        orig_pos = getattr(orig["ligand"], "orig_pos", None)
-        if orig_pos is not None:   # crystal pose known: RMSD metrics
-            if isinstance(orig_pos, list):
-                orig_pos = orig_pos[0]
-            orig_pos = np.asarray(orig_pos, dtype=np.float32)
-            orig_pos = orig_pos[None] if orig_pos.ndim == 2 else orig_pos
-            filterHs = torch.not_equal(predictions_list[0]["ligand"].x[:, 0], 0).cpu().numpy()
-            lp = ligand_pos[:, filterHs]
-            ref = orig_pos[:, filterHs] - orig.original_center.cpu().numpy()
-            mol = getattr(orig, "mol", None)
-            mol = mol[0] if isinstance(mol, (list, tuple)) else mol
-            mol = remove_all_hs(mol)          # RemoveAllHs(orig_complex_graph.mol[0]) in the reference; the coordinates are filtered with filterHs
-            per_ref = []
-            for r in ref:
-                try:
-                    per_ref.append(np.asarray(get_symmetry_rmsd(mol, r, [l for l in lp], device=device)))
-                except Exception as e:
-                    print("Using non corrected RMSD because of the error:", e)
-                    per_ref.append(np.sqrt(((lp - r) ** 2).sum(axis=2).mean(axis=1)))
-            rmsd = np.min(np.asarray(per_ref), axis=0)
-            rmsds.extend(rmsd.tolist())
-            min_rmsds.append(rmsd.min())
-            if confidences is not None:
-                top_rmsds.append(rmsd[int(np.argmax(np.asarray([float(c) for c in confidences])))])
-            if getattr(args, "oracle_confidence", False):
-                confidences = -4 * np.tanh(2 * rmsd / 3 - 2)
-        if confidences is None:
-            continue
-        confidences_list.extend(float(c) for c in confidences)
-        complexes_to_keep.extend((predictions_list[i], float(confidences[i])) for i in range(len(predictions_list))
-                                 if float(confidences[i]) > confidence_cutoff)
-    rmsds, min_rmsds, top_rmsds, conf = (np.asarray(x, dtype=np.float64) for x in (rmsds, min_rmsds, top_rmsds, confidences_list))
-    pct = lambda a, thr, n: float(100 * (a < thr).sum() / n) if n else None
-    losses = {"rmsds_lt2": pct(rmsds, 2, len(rmsds)), "rmsds_lt5": pct(rmsds, 5, len(rmsds)),
-              "filtered_rmsds_lt2": pct(top_rmsds, 2, len(min_rmsds)), "filtered_rmsds_lt5": pct(top_rmsds, 5, len(min_rmsds)),
-              "min_rmsds_lt2": pct(min_rmsds, 2, len(min_rmsds)), "min_rmsds_lt5": pct(min_rmsds, 5, len(min_rmsds)),
-              "avg_confidence": float(conf.mean()) if len(conf) else None,
-              "median_confidence": float(np.median(conf)) if len(conf) else None}
-    return losses, complexes_to_keep, top_rmsds
+    return summarize_inference(results, args, filtering_args, confidence_cutoff, device, group=group)
 
 
 class _Loader:

@@ -56,6 +56,140 @@ def graph_isomorphisms(atomicnums, adjacency, atomicnums2=None, adjacency2=None,
     return idx1, idx2
 
 
+# Isomorphisms of a ligand, enumerated once per process.  The fine-tuning loop measures the same ~100 ligands in every inference
+# iteration of every epoch, and once per crystal pose; the enumeration above is Python and can take its whole 10 s.
+#   * keyed on a digest of both graphs (atomic numbers, adjacency bits) and the count cap; not on names or object identity;
+#   * an enumeration that raised (IsomorphismLimit, ValueError) is an entry too and is re-raised from it: a ligand that times out pays once;
+#   * an entry also holds the device copies of its index tables (evaluation.pose_metrics_batch keeps them resident between calls),
+#     and its size counts host and device bytes;
+#   * least-recently-used entries are evicted by bytes (default limit 256 MB), never the whole cache at once;
+#   * only `cached_isomorphisms` (and through it pose_metrics_batch) uses it: graph_isomorphisms / symmetry_rmsd / get_symmetry_rmsd enumerate as before.
+_ISO_CACHE = __import__("collections").OrderedDict()      # key -> {"iso": (idx1, idx2) or None, "exc": (exception type, args) or None, "dev": {device key: (d1, d2)}, "bytes": int}
+_ISO_CACHE_BYTES = [0]
+_ISO_CACHE_CFG = {"enabled": True, "limit": 256 << 20}
+_ISO_CACHE_COUNT = {"hits": 0, "misses": 0}
+_ISO_ENTRY_OVERHEAD = 256      # bytes charged per entry on top of its tables (key, dict, a cached exception)
+
+
+def iso_cache_configure(enabled=None, limit_bytes=None):
+    if enabled is not None:
+        _ISO_CACHE_CFG["enabled"] = bool(enabled)
+        if not enabled:
+            iso_cache_clear()
+    if limit_bytes is not None:
+        _ISO_CACHE_CFG["limit"] = int(limit_bytes)
+        _iso_cache_evict(0)
+
+
+def iso_cache_clear():
+    _ISO_CACHE.clear()
+    _ISO_CACHE_BYTES[0] = 0
+    _ISO_CACHE_COUNT.update(hits=0, misses=0)
+
+
+def iso_cache_stats():
+    return {"entries": len(_ISO_CACHE), "bytes": _ISO_CACHE_BYTES[0], "hits": _ISO_CACHE_COUNT["hits"], "misses": _ISO_CACHE_COUNT["misses"]}
+
+
+def _iso_cache_evict(incoming, keep=None):
+    """drop least-recently-used entries (never `keep`) until `incoming` more bytes fit under the limit"""
+    for key in list(_ISO_CACHE):
+        if _ISO_CACHE_BYTES[0] + incoming <= _ISO_CACHE_CFG["limit"]:
+            break
+        if key != keep:
+            _ISO_CACHE_BYTES[0] -= _ISO_CACHE.pop(key)["bytes"]
+
+
+def isomorphism_key(atomicnums, adjacency, atomicnums2=None, adjacency2=None, max_isomorphisms=None):
+    """digest of both molecular graphs: atomic numbers and adjacency bits (any non-zero entry is a bond), plus the count cap in force"""
+    import hashlib
+    h = hashlib.blake2b(digest_size=20)
+    second = atomicnums2 is not None or adjacency2 is not None
+    a1, m1 = np.asarray(atomicnums), np.asarray(adjacency)
+    graphs = [(a1, m1)] + ([(a1 if atomicnums2 is None else np.asarray(atomicnums2), m1 if adjacency2 is None else np.asarray(adjacency2))]
+                           if second else [])
+    for nums, adj in graphs:
+        nums = np.ascontiguousarray(nums, dtype=np.int64).reshape(-1)
+        h.update(np.int64(len(nums)).tobytes())
+        h.update(nums.tobytes())
+        h.update(np.asarray(adj.shape, dtype=np.int64).tobytes())
+        h.update(np.packbits(np.asarray(adj) != 0).tobytes())
+    h.update(np.int64(MAX_ISOMORPHISMS if max_isomorphisms is None else max_isomorphisms).tobytes())
+    return h.hexdigest()
+
+
+def _iso_entry(atomicnums, adjacency, atomicnums2=None, adjacency2=None, max_isomorphisms=None, time_limit_s=None):
+    """the cache entry of a pair of graphs (enumerating on a miss); with the cache off, a fresh entry that is not kept"""
+    key = isomorphism_key(atomicnums, adjacency, atomicnums2, adjacency2, max_isomorphisms)
+    entry = _ISO_CACHE.get(key) if _ISO_CACHE_CFG["enabled"] else None
+    if entry is not None:
+        _ISO_CACHE.move_to_end(key)
+        _ISO_CACHE_COUNT["hits"] += 1
+        return key, entry
+    _ISO_CACHE_COUNT["misses"] += 1
+    entry = {"iso": None, "exc": None, "dev": {}, "bytes": _ISO_ENTRY_OVERHEAD}
+    try:
+        idx1, idx2 = graph_isomorphisms(atomicnums, adjacency, atomicnums2, adjacency2, max_isomorphisms, time_limit_s)
+        idx1.setflags(write=False)
+        idx2.setflags(write=False)
+        entry["iso"] = (idx1, idx2)
+        entry["bytes"] += idx1.nbytes + idx2.nbytes
+    except (IsomorphismLimit, ValueError) as e:
+        entry["exc"] = (type(e), e.args)      # not the exception itself: it would keep the frames of the enumeration alive
+    if _ISO_CACHE_CFG["enabled"] and entry["bytes"] <= _ISO_CACHE_CFG["limit"]:
+        _iso_cache_evict(entry["bytes"])
+        _ISO_CACHE[key] = entry
+        _ISO_CACHE_BYTES[0] += entry["bytes"]
+    return key, entry
+
+
+def cached_isomorphisms(atomicnums, adjacency, atomicnums2=None, adjacency2=None, max_isomorphisms=None, time_limit_s=None):
+    """graph_isomorphisms through the process-wide cache (policy: comment above): the same (idx1 [K,N], idx2 [K,N]) arrays, read-only
+    and shared between callers; an IsomorphismLimit / ValueError of the first enumeration is raised again without enumerating."""
+    _, entry = _iso_entry(atomicnums, adjacency, atomicnums2, adjacency2, max_isomorphisms, time_limit_s)
+    if entry["exc"] is not None:
+        raise entry["exc"][0](*entry["exc"][1])
+    return entry["iso"]
+
+
+def _identity_entry(n):
+    """the identity mapping of n atoms (K = 1) as a cache entry, so that its device copy stays resident like any ligand's tables"""
+    key = ("identity", int(n))
+    entry = _ISO_CACHE.get(key) if _ISO_CACHE_CFG["enabled"] else None
+    if entry is not None:
+        _ISO_CACHE.move_to_end(key)
+        return key, entry
+    idx = np.arange(int(n), dtype=np.int32)[None]
+    idx.setflags(write=False)
+    entry = {"iso": (idx, idx), "exc": None, "dev": {}, "bytes": _ISO_ENTRY_OVERHEAD + 2 * idx.nbytes}
+    if _ISO_CACHE_CFG["enabled"] and entry["bytes"] <= _ISO_CACHE_CFG["limit"]:
+        _iso_cache_evict(entry["bytes"])
+        _ISO_CACHE[key] = entry
+        _ISO_CACHE_BYTES[0] += entry["bytes"]
+    return key, entry
+
+
+def _iso_device_tables(key, entry, device):
+    """device copies (int32, contiguous) of an entry's index tables, uploaded on first use and kept in the entry: their bytes count
+    towards the cache limit, and they go when the entry is evicted (the caching allocator keeps the memory valid for work already queued
+    on the current stream)."""
+    dev = torch.device(device)
+    dkey = (dev.type, dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0))
+    hit = entry["dev"].get(dkey)
+    if hit is not None:
+        return hit
+    idx1, idx2 = entry["iso"]
+    d1 = torch.from_numpy(np.array(idx1, dtype=np.int32, order="C")).to(dev)
+    d2 = d1 if idx2 is idx1 else torch.from_numpy(np.array(idx2, dtype=np.int32, order="C")).to(dev)
+    entry["dev"][dkey] = (d1, d2)
+    if _ISO_CACHE.get(key) is entry:
+        added = d1.numel() * 4 * (1 if d2 is d1 else 2)
+        entry["bytes"] += added
+        _ISO_CACHE_BYTES[0] += added
+        _iso_cache_evict(0, keep=key)
+    return d1, d2
+
+
 def symmetry_rmsd(coords_ref, coords, atomicnums, adjacency, atomicnums2=None, adjacency2=None, device=None,
                   return_permutation=False, isomorphisms=None):
     """spyrmsd.rmsd.symmrmsd(coords_ref, coords, atomicnums, atomicnums2, adjacency, adjacency2) for one pose [N,3] or a

@@ -527,6 +527,7 @@ def inference_epoch_fix(model, complex_graphs, device, t_to_sigma, args):
     net = getattr(model, "module", model)
     net.eval()
     rmsds, min_rmsds = [], []
+    device_metrics, pending, METRICS_GROUP = bool(getattr(args, "device_metrics", False)), [], 8
     for orig in complex_graphs:
         orig = orig if isinstance(orig, Batch) else Batch.from_data_list([orig])
         data_list = [orig.shallow_copy() if hasattr(orig, "shallow_copy") else copy.deepcopy(orig) for _ in range(args.inference_samples)]
@@ -560,6 +561,11 @@ def inference_epoch_fix(model, complex_graphs, device, t_to_sigma, args):
         mol = getattr(orig, "mol", None)
         mol = mol[0] if isinstance(mol, (list, tuple)) else mol
         mol = remove_all_hs(mol)          # RemoveAllHs(orig_complex_graph.mol[0]) in the reference; the coordinates are filtered with filterHs
+        if device_metrics:      # opt-in: measured after the loop, METRICS_GROUP complexes per launch; the slots keep the order
+            pending.append((len(rmsds), len(min_rmsds), (ligand_pos, ref, mol)))
+            rmsds.extend([None] * len(ligand_pos))
+            min_rmsds.append(None)
+            continue
         per_ref = []
         for r in ref:
             try:
@@ -570,6 +576,13 @@ def inference_epoch_fix(model, complex_graphs, device, t_to_sigma, args):
         rmsd = np.min(np.asarray(per_ref), axis=0)
         rmsds.extend(rmsd.tolist())
         min_rmsds.append(rmsd.min())
+    for k in range(0, len(pending), METRICS_GROUP):      # evaluation.pose_metrics_batch: cached isomorphisms, one upload / launch / download per group
+        from .evaluation import pose_metrics_batch
+        part = pending[k:k + METRICS_GROUP]
+        for (at, at_min, _), out in zip(part, pose_metrics_batch([it[2] for it in part], device)):
+            rmsd = out[0].astype(np.float64)
+            rmsds[at:at + len(rmsd)] = rmsd.tolist()
+            min_rmsds[at_min] = rmsd.min()
     rmsds, min_rmsds = np.asarray(rmsds, dtype=np.float64), np.asarray(min_rmsds, dtype=np.float64)
     return {"rmsds_lt2": 100 * (rmsds < 2).sum() / len(rmsds), "rmsds_lt5": 100 * (rmsds < 5).sum() / len(rmsds),
             "min_rmsds_lt2": 100 * (min_rmsds < 2).sum() / len(min_rmsds), "min_rmsds_lt5": 100 * (min_rmsds < 5).sum() / len(min_rmsds)}

@@ -281,6 +281,32 @@ int cbd_randomize_poses(int32_t n_poses, int32_t n_ligands, int32_t n_complexes,
                         const int32_t* mask_ptr_dev, const uint32_t* mask_bits_dev, const double* tor_dev, const float* rot_mat_dev,
                         const float* tr_dev, const float* center_dev, float* pos_out_dev, void* stream);
 
+/* What an inference epoch measures on its sampled poses (reference inference.py:505-548, finetune_train.py:205-214), for n_poses
+ * poses of n_complexes complexes in one launch, one 256-thread workgroup per pose.  Complex c has N = cplx_n[c] heavy atoms, K = cplx_k[c]
+ * graph isomorphisms idx_ref_tab[c] / idx_pos_tab[c] -> [K][N] int32 (isomorphism k maps crystal atom idx_ref[k][i] to pose atom
+ * idx_pos[k][i]; enumerated on the host) and Q = cplx_q[c] >= 1 crystal poses ref[ref_ptr[c] ..][Q][N][3]; pose p belongs to complex
+ * pose_cplx[p] and has its N atoms at pos[pose_ptr[p] ..][3].  pose_ptr [n_poses + 1] and ref_ptr [n_complexes + 1] are prefix sums
+ * in atoms.  The two pointer tables are arrays of n_complexes DEVICE pointers in device memory: a ligand's index tables may stay
+ * resident between calls and be shared by several complexes.  Per pose:
+ *   rmsd       = min over q of float(sqrt(min_k S(q, k) / N)), S(q, k) = sum_i |ref_q[idx_ref[k][i]] - pos[idx_pos[k][i]]|^2 accumulated
+ *                in fp64 exactly as cbd_symm_rmsd does: bitwise what that entry returns per crystal pose, followed by a minimum over them;
+ *   argmin_ref = the lowest q that attains it (compared as fp32, like the minimum above), argmin_iso = the lowest k that attains
+ *                min_k S(q, k) for that q (compared as fp64: the first minimum wins, as in cbd_symm_rmsd);
+ *   centroid   = min over q of |mean(pos) - mean(ref_q)|;  min_self = the smallest distance between two different atoms of the pose
+ *                (inf for N = 1); both fp64 on the fp32 coordinates, rounded to fp32 once.
+ * max_n: the largest N of the launch; max_ref_atoms: the largest Q * N.  Capacity N <= 512, Q * N <= 4096: larger values return
+ * CBD_ERR_CAPACITY and nothing is launched or written.  A pose whose description contradicts itself -- pose_cplx names no complex,
+ * N outside [1, max_n], K < 1, Q < 1, Q * N > max_ref_atoms, pose_ptr / ref_ptr extents that differ from N / Q * N or start below 0,
+ * a NULL index table, or an index outside [0, N) in its tables -- gets NaN in the three fp32 outputs and -1 in both argmins; the
+ * kernel indexes with none of these before it has checked it (the lengths of the ragged arrays and of the index tables themselves
+ * are the caller's: the kernel cannot know them).  No atomics, no scratch memory: bitwise repeatable, and a pose's result does not
+ * depend on what shares the launch.  n_poses = 0 returns 0 without a launch.  Device pointers; asynchronous on `stream`. */
+int cbd_pose_metrics(int32_t n_poses, int32_t n_complexes, int32_t max_n, int32_t max_ref_atoms, const int32_t* pose_cplx_dev,
+                     const int32_t* pose_ptr_dev, const float* pos_dev, const int32_t* cplx_n_dev, const int32_t* cplx_k_dev,
+                     const int32_t* cplx_q_dev, const int32_t* ref_ptr_dev, const float* ref_dev, const int32_t* const* idx_ref_tab_dev,
+                     const int32_t* const* idx_pos_tab_dev, float* rmsd_out_dev, float* centroid_out_dev, float* min_self_out_dev,
+                     int32_t* argmin_ref_out_dev, int32_t* argmin_iso_out_dev, void* stream);
+
 /* ============================ all-atom CONFIDENCE model ===========================================
  * Replaces, for the shipped workdir/pretrained_confidence architecture, the confidence branch of
  * utils/sampling.py:240-261: crop_beyond (utils/utils.py:395-420) + set_time(0) + the all-atom
