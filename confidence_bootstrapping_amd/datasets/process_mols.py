@@ -457,11 +457,43 @@ def _lig_graph_from_matched_conformers(mol_, complex_graph, conformers, popsize,
     return picked
 
 
+def generate_conformer(mol, seed=0, device=None):
+    """Reference process_mols.py:591-607 with the GPU distance-geometry embedding (datasets/conformer_embedding.py) in place of rdkit's
+    ETKDG: up to 3 attempts with fresh conformer ids under `seed`; the first that passes the acceptance test becomes the coordinates of
+    `mol` and False is returned.  If none passes, the least-violating one is taken and True ("fell back") is returned.  The molecule's
+    own pose (if it has one that is not flat) fixes the handedness.  The three attempts share one launch."""
+    from . import conformer_embedding as ce
+    if not mol.perceived:
+        perceive(mol)
+    ref = mol.GetConformer().GetPositions() if mol.GetNumConformers() else None
+    pos, ok, err = ce.embed_conformers(mol, 3, seed=seed, ref_pos=ref, device=device)
+    good = np.nonzero(ok)[0]
+    pick = int(good[0]) if len(good) else int(np.argmin(err))
+    mol.pos = pos[pick].copy()
+    return len(good) == 0
+
+
+def _embedded_conformers(mol_, remove_hs, num_conformers, tries, seed):
+    """The (hydrogen-stripped, if remove_hs) molecule and num_conformers * tries embedded conformers of it, handedness from its pose."""
+    import copy
+    from . import conformer_embedding as ce
+    mol = copy.deepcopy(mol_)
+    if not mol.perceived:
+        perceive(mol)
+    if remove_hs:
+        mol = _remove_hs(mol)
+    pos, _, _ = ce.embed_until_ok(mol, int(num_conformers) * int(tries), seed=seed, ref_pos=mol.GetConformer().GetPositions())
+    return mol, list(pos)
+
+
 def get_lig_graph_with_matching(mol_, complex_graph, popsize=None, maxiter=None, matching=False, keep_original=False, num_conformers=1,
-                                remove_hs=False, tries=10, skip_matching=False, conformers=None):
+                                remove_hs=False, tries=10, skip_matching=False, conformers=None, seed=0):
     """Reference process_mols.py:609-657.  `matching=False`: poses as given in the file (what inference on holo ligands uses).
-    `matching=True`: the reference embeds `tries` fresh conformers per requested conformer with rdkit's ETKDG -- not built -- and
-    matches each to the holo pose; here the conformers come from the caller.  `conformers`: a sequence of [N, 3] arrays (or of
+    `matching=True`: the reference embeds `tries` fresh conformers per requested conformer with rdkit's ETKDG and matches each to the
+    holo pose; here the conformers come from the caller, or -- `conformers="embed"` -- from the GPU distance-geometry embedding of
+    datasets/conformer_embedding.py (num_conformers * tries conformers of the hydrogen-stripped molecule in one launch under `seed`,
+    handedness from the holo pose, a conformer that fails the acceptance test replaced from further ids).  `conformers=None` raises
+    NotImplementedError: nothing is embedded unasked.  `conformers`: a sequence of [N, 3] arrays (or of
     `Mol`s, or one `Mol`) in the atom order of `mol_`, `num_conformers` consecutive groups of `tries` (a shorter last group is
     taken as it is).  Every one is torsion-matched on the GPU (datasets/conformer_matching.py) unless `skip_matching` or the molecule
     has no rotatable bond, aligned onto the holo pose, and the one with the lowest RMSD of each group is kept: the first builds the
@@ -469,6 +501,11 @@ def get_lig_graph_with_matching(mol_, complex_graph, popsize=None, maxiter=None,
     if matching:
         if conformers is None:
             raise NotImplementedError("generating conformers needs rdkit (ETKDG embedding); pass conformers=..., or call with matching=False")
+        if isinstance(conformers, str):
+            if conformers != "embed":
+                raise ValueError(f"conformers={conformers!r}: pass coordinates, or \"embed\"")
+            mol_, conformers = _embedded_conformers(mol_, remove_hs, num_conformers, tries, seed)
+            remove_hs = False                      # done: the conformers are those of the stripped molecule
         mol_ = _lig_graph_from_matched_conformers(mol_, complex_graph, conformers, popsize, maxiter, keep_original, num_conformers,
                                                   remove_hs, tries, skip_matching)
     else:

@@ -307,6 +307,36 @@ int cbd_pose_metrics(int32_t n_poses, int32_t n_complexes, int32_t max_n, int32_
                      const int32_t* const* idx_pos_tab_dev, float* rmsd_out_dev, float* centroid_out_dev, float* min_self_out_dev,
                      int32_t* argmin_ref_out_dev, int32_t* argmin_iso_out_dev, void* stream);
 
+/* Ligand conformers by distance geometry (the first half of the reference's conformer matching: generate_conformer,
+ * datasets/process_mols.py:591-607, rdkit's ETKDG there; here plain distance geometry along rdkit's useRandomCoords route, see
+ * DESIGN.md section 9 and csrc/conformer_embed.hip).  n_conformers conformers of n_mols molecules in one launch, one workgroup of 4
+ * waves per conformer.  Molecule m has N = mol_n[m] atoms, symmetric triangle-smoothed distance bounds lower / upper [N][N] at
+ * element bnd_ptr[m] of lower_dev / upper_dev (bnd_ptr [n_mols + 1] = prefix sums of N^2) and nc = cons_ptr[m + 1] - cons_ptr[m]
+ * constraints on quadruples of its atoms, cons_idx [.][4] (distinct LOCAL indices), cons_lo / cons_hi, cons_kind:
+ *   0  the volume V = (p1 - p0) . ((p2 - p0) x (p3 - p0)) lies in [lo, hi];   1  |V| lies in [lo, hi];
+ *   2  planarity: p0 lies within hi of the plane through p1, p2, p3.
+ * The bounds of a molecule are shared by its conformers: conformer c belongs to molecule conf_mol[c] and writes its N coordinates at
+ * pos_out[out_ptr[c] ..][3] (out_ptr [n_conformers + 1], prefix sums in atoms).  Stages: random 4-D coordinates in a box; FIRE
+ * minimisation of rdkit's distance-violation error ((d^2 / ub^2 - 1)^2 above the upper bound, (2 lb^2 / (lb^2 + d^2) - 1)^2 below the
+ * lower) plus the volume terms with the fourth dimension weakly penalised (at most iters_4d_weak iterations), again with it strongly
+ * penalised (iters_4d_strong), then in 3-D with the planarity terms (iters_3d).  Random numbers are a hash of (seed, mol_id[m] (NULL:
+ * m), conf_id[c], atom, dimension); every sum has a fixed order and there are no atomics, so a conformer is bitwise repeatable and
+ * does not depend on what shares the launch.
+ * Outputs per conformer: pos_out; err_out = the final value of the 3-D objective; ok_out = 1 when every pair distance lies in
+ * [lower - bound_tol, upper + bound_tol], every volume in its interval and every planarity height under its limit, else 0.
+ * max_n / max_constraints: the largest N / nc of the launch.  Capacity N <= 256, nc <= 1024: larger values return CBD_ERR_CAPACITY
+ * and nothing is launched or written.  A conformer whose description contradicts itself -- conf_mol names no molecule, N outside
+ * [1, max_n], nc outside [0, max_constraints], bnd_ptr / out_ptr extents that differ from N^2 / N or start below 0, a constraint with
+ * an index outside [0, N), a repeated index or an unknown kind -- gets ok = -1 and err = NaN and its coordinates are left unwritten;
+ * the kernel indexes with none of these before it has checked it (the lengths of the arrays themselves are the caller's).
+ * n_conformers = 0 returns 0 without a launch.  Device pointers; asynchronous on `stream`. */
+int cbd_embed_conformers(int32_t n_mols, int32_t n_conformers, int32_t max_n, int32_t max_constraints, const int32_t* mol_n_dev,
+                         const int32_t* bnd_ptr_dev, const float* lower_dev, const float* upper_dev, const int32_t* cons_ptr_dev,
+                         const int32_t* cons_idx_dev, const float* cons_lo_dev, const float* cons_hi_dev, const int32_t* cons_kind_dev,
+                         const int32_t* mol_id_dev, const int32_t* conf_mol_dev, const int32_t* conf_id_dev, const int32_t* out_ptr_dev,
+                         uint64_t seed, int32_t iters_4d_weak, int32_t iters_4d_strong, int32_t iters_3d, float bound_tol, float* pos_out_dev,
+                         float* err_out_dev, int32_t* ok_out_dev, void* stream);
+
 /* ============================ all-atom CONFIDENCE model ===========================================
  * Replaces, for the shipped workdir/pretrained_confidence architecture, the confidence branch of
  * utils/sampling.py:240-261: crop_beyond (utils/utils.py:395-420) + set_time(0) + the all-atom
