@@ -91,6 +91,8 @@ struct cbd_engine {
   std::vector<GraphEntry> graphs;
   float *g_pos = nullptr, *g_ztr = nullptr, *g_zrot = nullptr, *g_ztor = nullptr;
   int g_S_cap = 0;
+  float* g_traj = nullptr;          // [g_traj_S][max_batch][Nl][3] staging of a recorded trajectory (cbd_sample_traj); allocated on first use
+  int g_traj_S = 0;
   // Generation stamp of everything a captured launch of this engine depends on (complex, staging buffers, weights).  Drawn from ONE
   // process-wide monotonic counter (next_gen), never from a per-engine 0: the graphs of a co-scheduled group live on its first engine
   // and are keyed by (engine address, generation) of every member, so a partner that is destroyed and re-created at the same heap
@@ -894,6 +896,7 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
   e->sync_all = false;
   drop_graphs(e);
   e->g_pos = nullptr; e->g_S_cap = 0;
+  e->g_traj = nullptr; e->g_traj_S = 0;
   e->cpool.reset(); e->bpool.reset();
   e->complex_ready = false;
   const int Bm = e->cfg.max_batch, lm = e->cfg.lm_embedding_dim;
@@ -1175,9 +1178,10 @@ static void fill_static_desc(cbd_engine* e) {
   }
 }
 
-// Per-call part of the descriptor -> device (stream ordered).
+// Per-call part of the descriptor -> device (stream ordered).  traj has no default on purpose: every call states whether the pose
+// update records (only cbd_sample_traj does), so a pointer of an earlier recording call cannot survive in the descriptor.
 static int push_desc(cbd_engine* e, int B, float* pos, float* tr, float* rot, float* tor, const float* ztr, const float* zrot,
-                     const float* ztor, hipStream_t s) {
+                     const float* ztor, float* traj, hipStream_t s) {
   PoseBatch& D = e->desc_h;
   D.B = B;
   D.cap_ll = B * e->cap_ll_per_sample;
@@ -1185,6 +1189,7 @@ static int push_desc(cbd_engine* e, int B, float* pos, float* tr, float* rot, fl
   D.gd.pos = pos;
   D.tr_out = tr; D.rot_out = rot; D.tor_out = tor;
   D.z_tr = ztr; D.z_rot = zrot; D.z_tor = ztor;
+  D.traj = traj;
   e->last_B = B;
   HIPCHK(launch_set_desc(D, e->desc_dev, s));
   return 0;
@@ -1359,7 +1364,7 @@ int cbd_score(cbd_engine* e, int32_t B, const float* pos_dev, const cbd_step* st
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   e->sync_all = true;
   HIPCHK(hipMemcpyAsync(e->sigma_emb_dev, step->sigma_emb, 64 * sizeof(float), hipMemcpyHostToDevice, s));   // sigma_emb | sigma_emb_t (adjacent)
-  CHK(push_desc(e, B, const_cast<float*>(pos_dev), tr_dev, rot_dev, tor_dev ? tor_dev : e->tor_out, nullptr, nullptr, nullptr, s));
+  CHK(push_desc(e, B, const_cast<float*>(pos_dev), tr_dev, rot_dev, tor_dev ? tor_dev : e->tor_out, nullptr, nullptr, nullptr, nullptr, s));
   cbd_engine* E[1] = {e};
   CHK(forward_multi(E, 1, *step, e->sigma_emb_dev, s));
   return 0;
@@ -1374,18 +1379,20 @@ int cbd_modify_conformer(cbd_engine* e, int32_t B, float* pos_dev, const float* 
   e->sync_all = true;
   // the given updates take the place of the scores (use_coefs = 0): descriptor outputs point at them
   CHK(push_desc(e, B, pos_dev, const_cast<float*>(tr_dev), const_cast<float*>(rot_dev), const_cast<float*>(tor_dev), nullptr, nullptr,
-                nullptr, s));
+                nullptr, nullptr, s));
   const PoseBatch* d[1] = {e->desc_dev};
   HIPCHK(launch_pose_update(make_multi(1, d, [&](int) { return B; }), 0, SdeCoefs{}, 0, tor_dev != nullptr && e->gs.R > 0, e->gs.Nl, s));
   return 0;
 }
 
-// The step loop of n co-scheduled batches (n = 1: cbd_sample).
+// The step loop of n co-scheduled batches (n = 1: cbd_sample).  traj_dev (or null): per batch a [S, B[k], Nl_k, 3] buffer that receives the
+// pose after every step, written by the pose update itself (descriptor field traj), or null.
 static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S, const cbd_step* steps, float* const* pos_dev,
                        const float* const* noise_tr, const float* const* noise_rot, const float* const* noise_tor, float* scores_out,
-                       hipStream_t s) {
+                       float* const* traj_dev, hipStream_t s) {
   cbd_engine* e0 = E[0];
   auto nz = [](const float* const* a, int k) { return a ? a[k] : nullptr; };
+  auto tj = [&](int k) -> float* { return traj_dev ? traj_dev[k] : nullptr; };
   if (S > e0->sigma_cap) {
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(e0->bpool.alloc(&e0->sigma_emb_dev, (size_t)S * 64));
@@ -1425,7 +1432,7 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
   for (int k = 0; k < n; ++k) graph_ok = graph_ok && !E[k]->keep_debug;
   if (!graph_ok) {
     for (int k = 0; k < n; ++k)
-      CHK(push_desc(E[k], B[k], pos_dev[k], E[k]->tr_out, E[k]->rot_out, E[k]->tor_out, nz(noise_tr, k), nz(noise_rot, k), nz(noise_tor, k), s));
+      CHK(push_desc(E[k], B[k], pos_dev[k], E[k]->tr_out, E[k]->rot_out, E[k]->tor_out, nz(noise_tr, k), nz(noise_rot, k), nz(noise_tor, k), tj(k), s));
     CHK(run_steps(scores_out));
     for (int k = 0; k < n; ++k) { HIPCHK(hipEventRecord(E[k]->ev_last, s)); E[k]->last_used = true; }
     return 0;   // asynchronous: kernel-timing events are collected when cbd_kernel_timing is queried
@@ -1451,16 +1458,22 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
       e->g_S_cap = S;
       e->complex_gen = cbd_engine::next_gen();
     }
+    if (tj(k) && e->g_traj_S < S) {   // first recording call of this complex (or a longer schedule)
+      HIPCHK(hipStreamSynchronize(s));
+      HIPCHK(e->bpool.alloc(&e->g_traj, (size_t)S * Bm * Nl * 3));
+      e->g_traj_S = S;
+    }
     char buf[96];
     snprintf(buf, sizeof buf, "|%p:%llu:%d:%d:%d:%d", (void*)e, (unsigned long long)e->complex_gen, (int)B[k], e->use_bf16 + 32 * e->bf16_stat,
              (nz(noise_tr, k) != nullptr) + 2 * (nz(noise_rot, k) != nullptr) + 4 * (nz(noise_tor, k) != nullptr), (int)e->timing);
     key += buf;
   }
-  // descriptors point at the staging buffers; refreshed before every launch (an eager call in between may have re-pointed them)
+  // descriptors point at the staging buffers; refreshed before every launch (an eager call in between may have re-pointed them).
+  // Whether a batch records lives in its descriptor alone (traj), not in a captured node: the graph key does not depend on it.
   for (int k = 0; k < n; ++k) {
     cbd_engine* e = E[k];
     CHK(push_desc(e, B[k], e->g_pos, e->tr_out, e->rot_out, e->tor_out, nz(noise_tr, k) ? e->g_ztr : nullptr,
-                  nz(noise_rot, k) ? e->g_zrot : nullptr, nz(noise_tor, k) ? e->g_ztor : nullptr, s));
+                  nz(noise_rot, k) ? e->g_zrot : nullptr, nz(noise_tor, k) ? e->g_ztor : nullptr, tj(k) ? e->g_traj : nullptr, s));
   }
   hipGraphExec_t exec = nullptr;
   for (auto& g : e0->graphs)
@@ -1496,6 +1509,8 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
   HIPCHK(hipGraphLaunch(exec, s));
   for (int k = 0; k < n; ++k)
     HIPCHK(hipMemcpyAsync(pos_dev[k], E[k]->g_pos, (size_t)B[k] * E[k]->gs.Nl * 3 * 4, hipMemcpyDeviceToDevice, s));
+  for (int k = 0; k < n; ++k)      // the staged rows are [S][B[k]] dense (the kernel strides by this call's B): one copy
+    if (tj(k)) HIPCHK(hipMemcpyAsync(tj(k), E[k]->g_traj, (size_t)S * B[k] * E[k]->gs.Nl * 3 * 4, hipMemcpyDeviceToDevice, s));
   for (int k = 0; k < n; ++k) { HIPCHK(hipEventRecord(E[k]->ev_last, s)); E[k]->last_used = true; }      // what an asynchronous cbd_set_complex of these engines waits for
   if (!user) {
     HIPCHK(hipEventRecord(e0->ev_b, s));
@@ -1515,11 +1530,12 @@ int cbd_sample(cbd_engine* e, int32_t B, int32_t S, const cbd_step* steps, float
   const float* tr[1] = {noise_tr};
   const float* rot[1] = {noise_rot};
   const float* tor[1] = {noise_tor};
-  return sample_impl(1, E, Bs, S, steps, ps, tr, rot, tor, scores_out, reinterpret_cast<hipStream_t>(stream));
+  return sample_impl(1, E, Bs, S, steps, ps, tr, rot, tor, scores_out, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-int cbd_sample_multi(int32_t n, cbd_engine* const* engines, const int32_t* B, int32_t S, const cbd_step* steps, float* const* pos_dev,
-                     const float* const* noise_tr, const float* const* noise_rot, const float* const* noise_tor, void* stream) {
+int cbd_sample_traj(int32_t n, cbd_engine* const* engines, const int32_t* B, int32_t S, const cbd_step* steps, float* const* pos_dev,
+                    const float* const* noise_tr, const float* const* noise_rot, const float* const* noise_tor, float* const* traj_dev,
+                    void* stream) {
   if (n < 1 || n > MAX_COSCHED || !engines || !B || !pos_dev) return fail(CBD_ERR_ARG, "1..%d engines are required", MAX_COSCHED);
   if (S <= 0 || !steps) return fail(CBD_ERR_ARG, "bad argument");
   cbd_engine* e0 = engines[0];
@@ -1539,7 +1555,12 @@ int cbd_sample_multi(int32_t n, cbd_engine* const* engines, const int32_t* B, in
     CHK(check_batch(e, B[k]));
   }
   HIPCHK(hipSetDevice(e0->cfg.device));
-  return sample_impl(n, engines, B, S, steps, pos_dev, noise_tr, noise_rot, noise_tor, nullptr, reinterpret_cast<hipStream_t>(stream));
+  return sample_impl(n, engines, B, S, steps, pos_dev, noise_tr, noise_rot, noise_tor, nullptr, traj_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cbd_sample_multi(int32_t n, cbd_engine* const* engines, const int32_t* B, int32_t S, const cbd_step* steps, float* const* pos_dev,
+                     const float* const* noise_tr, const float* const* noise_rot, const float* const* noise_tor, void* stream) {
+  return cbd_sample_traj(n, engines, B, S, steps, pos_dev, noise_tr, noise_rot, noise_tor, nullptr, stream);
 }
 
 int cbd_sample_pair(cbd_engine* e0, cbd_engine* e1, int32_t B0, int32_t B1, int32_t S, const cbd_step* steps, float* pos0_dev,

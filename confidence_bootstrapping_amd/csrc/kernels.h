@@ -66,6 +66,7 @@ struct PoseBatch {
   float *center_msg, *dbg_global, *dbg_torfeat;
   int *tor_nb, *tor_nb_cnt;
   const float *z_tr, *z_rot, *z_tor;   // pre-drawn noise of the whole call [S][B][3], [S][B][3], [S][B*R] (or null)
+  float* traj;                   // [S][B][Nl][3]: the pose after every step of a sampling call (B = this call's), or null = not recorded
   unsigned long long* stats;     // [4] work counters
   FinArgs fin_emb, fin_lig, fin_rec, fin_rec_shared;   // segmented-sum descriptions of the layer kinds (static per complex)
 };

@@ -584,6 +584,8 @@ __global__ __launch_bounds__(64) void pose_update_kernel(Multi mm, int step, Sde
   float* flex = sp;
   float* rigid = sp + 3 * Nl;
   float* P = pos + (size_t)b * Nl * 3;
+  // trajectory row of this step and sample: the pose written below is stored there as well (sampling calls that record only)
+  float* __restrict__ T = (use_coefs && PB.traj) ? PB.traj + ((size_t)step * B + b) * Nl * 3 : nullptr;
   // perturbations
   float trp[3], rotp[3];
 #pragma unroll
@@ -613,6 +615,8 @@ __global__ __launch_bounds__(64) void pose_update_kernel(Multi mm, int step, Sde
   __syncthreads();
   if (tor == nullptr || R == 0) {
     for (int a = lane; a < Nl; a += 64) { P[3 * a] = rigid[3 * a]; P[3 * a + 1] = rigid[3 * a + 1]; P[3 * a + 2] = rigid[3 * a + 2]; }
+    if (T)
+      for (int a = lane; a < Nl; a += 64) { T[3 * a] = rigid[3 * a]; T[3 * a + 1] = rigid[3 * a + 1]; T[3 * a + 2] = rigid[3 * a + 2]; }
     return;
   }
   // sequential torsions on the already-updated coordinates
@@ -688,9 +692,11 @@ __global__ __launch_bounds__(64) void pose_update_kernel(Multi mm, int step, Sde
   const float tz = fb[2] - (Rk[6] * fa[0] + Rk[7] * fa[1] + Rk[8] * fa[2]);
   for (int a = lane; a < Nl; a += 64) {
     const float fx = flex[3 * a], fy = flex[3 * a + 1], fz = flex[3 * a + 2];
-    P[3 * a] = Rk[0] * fx + Rk[1] * fy + Rk[2] * fz + tx;
-    P[3 * a + 1] = Rk[3] * fx + Rk[4] * fy + Rk[5] * fz + ty;
-    P[3 * a + 2] = Rk[6] * fx + Rk[7] * fy + Rk[8] * fz + tz;
+    const float ox = Rk[0] * fx + Rk[1] * fy + Rk[2] * fz + tx;
+    const float oy = Rk[3] * fx + Rk[4] * fy + Rk[5] * fz + ty;
+    const float oz = Rk[6] * fx + Rk[7] * fy + Rk[8] * fz + tz;
+    P[3 * a] = ox; P[3 * a + 1] = oy; P[3 * a + 2] = oz;
+    if (T) { T[3 * a] = ox; T[3 * a + 1] = oy; T[3 * a + 2] = oz; }
   }
 }
 

@@ -549,3 +549,38 @@ def get_complex(protein_pdb, ligand_file, name, device, remove_hs=True, mol2_fil
     g.receptor_name = rec.receptor_name
     g["ligand"].pos = g["ligand"].pos - rec.original_center
     return g
+
+
+_SDF_CHARGE_CODE = {1: 3, 2: 2, 3: 1, -1: 5, -2: 6, -3: 7}
+
+
+def write_mol_with_coords(mol: Mol, new_coords, path):
+    """Reference process_mols.py:914-921 (an rdkit SDWriter on the molecule with its conformer replaced) for a `molfile.Mol`: one V2000
+    record with the atoms, the bonds with their types (aromatic = 4, unspecified = 8), formal charges (atom block code and M  CHG), the
+    radicals the reader keeps (M  RAD) and the name of `mol`, at the coordinates `new_coords` [N, 3] (%10.4f), closed by `$$$$`.
+    `mol` itself is not modified.  The fixed-width count and index fields hold three digits: more than 999 atoms or bonds, and a
+    coordinate that does not fit its ten columns, are a ValueError."""
+    if torch.is_tensor(new_coords):
+        new_coords = new_coords.detach().cpu().numpy()
+    xyz = np.asarray(new_coords, dtype=np.float64).reshape(-1, 3)
+    atoms, bonds = mol.GetAtoms(), mol.GetBonds()
+    if len(atoms) > 999 or len(bonds) > 999:
+        raise ValueError(f"a V2000 connection table holds at most 999 atoms and 999 bonds (got {len(atoms)}, {len(bonds)})")
+    if xyz.shape[0] != len(atoms):
+        raise ValueError(f"{xyz.shape[0]} coordinates for {len(atoms)} atoms")
+    if not np.isfinite(xyz).all() or xyz.max(initial=0.0) >= 99999.99995 or xyz.min(initial=0.0) <= -9999.99995:
+        raise ValueError("coordinates must be finite and fit the ten columns of a V2000 atom line")
+    lines = [str(mol.name or "").splitlines()[0] if str(mol.name or "").strip() else "", "  confidence_bootstrapping_amd          3D", "",
+             "%3d%3d  0  0  0  0  0  0  0  0999 V2000" % (len(atoms), len(bonds))]
+    for a, (x, y, z) in zip(atoms, xyz):
+        lines.append("%10.4f%10.4f%10.4f %-3s 0%3d  0  0  0  0  0  0  0  0  0  0" % (x, y, z, a.symbol, _SDF_CHARGE_CODE.get(a.charge, 0)))
+    for b in bonds:
+        lines.append("%3d%3d%3d  0" % (b.a + 1, b.b + 1, b.type if b.type in (1, 2, 3, 4) else 8))
+    for tag, vals in (("CHG", [(a.idx + 1, a.charge) for a in atoms if a.charge]),
+                      ("RAD", [(a.idx + 1, 2 if a.radicals == 1 else 3) for a in atoms if a.radicals])):
+        for lo in range(0, len(vals), 8):
+            part = vals[lo:lo + 8]
+            lines.append("M  %s%3d" % (tag, len(part)) + "".join("%4d%4d" % v for v in part))
+    lines += ["M  END", "$$$$"]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")

@@ -54,6 +54,7 @@ SYMBOLS = {
     "cbd_sample": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(cbd_step), _P, _P, _P, _P, _P, _P]),
     "cbd_sample_pair": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(cbd_step)] + [_P] * 9),
     "cbd_sample_multi": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(cbd_step), _P, _P, _P, _P, _P]),
+    "cbd_sample_traj": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(cbd_step), _P, _P, _P, _P, _P, _P]),
     "cbd_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "cbd_share_weights": (C.c_int, [_P, _P]),
     "cbd_recompute_receptor": (C.c_int, [_P, _P]),
@@ -308,12 +309,23 @@ class DockEngine:
             _check(self.lib.cbd_modify_conformer(self.h, B, _dptr(pos), _dptr(tr), _dptr(rot), _dptr(tor), self._stream()))
         return pos
 
-    def sample(self, pos, steps, noise_tr=None, noise_rot=None, noise_tor=None, return_scores=False):
-        """In-place reverse diffusion of pos [B,Nl,3] (device tensor) over len(steps) steps."""
+    def sample(self, pos, steps, noise_tr=None, noise_rot=None, noise_tor=None, return_scores=False, trajectory=False):
+        """In-place reverse diffusion of pos [B,Nl,3] (device tensor) over len(steps) steps.  trajectory=True: also returns the pose
+        after every step as a device tensor [S,B,Nl,3] (cbd_sample_traj; frame S-1 is the final pose); with return_scores=True as
+        well: (scores, trajectory), stepped one cbd_sample call per step (the per-step scores exist on that eager path only)."""
         B, S = pos.shape[0], len(steps)
         assert pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous()
         f = lambda x: None if x is None else x.to(self.device, torch.float32).contiguous()
         noise_tr, noise_rot, noise_tor = f(noise_tr), f(noise_rot), f(noise_tor)
+        if trajectory and return_scores:
+            row = lambda z, k: None if z is None else z[k:k + 1]
+            scores, frames = [], []
+            for k in range(S):
+                scores.append(self.sample(pos, (cbd_step * 1)(steps[k]), row(noise_tr, k), row(noise_rot, k), row(noise_tor, k), return_scores=True))
+                frames.append(pos.clone())
+            return torch.cat(scores), torch.stack(frames)
+        if trajectory:
+            return DockEngine.sample_multi([self], [pos], steps, [(noise_tr, noise_rot, noise_tor)], trajectory=True)[0]
         scores = torch.empty(S, B * (6 + self.R), device=self.device) if return_scores else None
         with torch.cuda.device(self.device):
             _check(self.lib.cbd_sample(self.h, B, S, steps, _dptr(pos), _dptr(noise_tr), _dptr(noise_rot), _dptr(noise_tor),
@@ -338,9 +350,11 @@ class DockEngine:
                                             _dptr(n1[2]), self._stream()))
 
     @staticmethod
-    def sample_multi(engines, poses, steps, noises):
+    def sample_multi(engines, poses, steps, noises, trajectory=False):
         """cbd_sample_multi: up to 8 engines (sharing weights, each with its own complex) advanced in lockstep with merged
-        tensor-product launches.  poses: list of [b,Nl,3] device tensors (updated in place); noises: list of (tr, rot, tor) or None."""
+        tensor-product launches.  poses: list of [b,Nl,3] device tensors (updated in place); noises: list of (tr, rot, tor) or None.
+        trajectory=True (cbd_sample_traj): returns a list of device tensors [S,b,Nl,3], the pose of every batch after every step;
+        a list of booleans records the chosen batches only (None in the place of the others)."""
         n = len(engines)
         e0 = engines[0]
         f = lambda x: None if x is None else x.to(e0.device, torch.float32).contiguous()
@@ -350,6 +364,14 @@ class DockEngine:
         arr = lambda vals: (C.c_void_p * n)(*[None if v is None else v.data_ptr() for v in vals])
         hs = (C.c_void_p * n)(*[e.h.value for e in engines])
         Bs = (C.c_int32 * n)(*[p.shape[0] for p in poses])
+        want = list(trajectory) if isinstance(trajectory, (list, tuple)) else [bool(trajectory)] * n
+        assert len(want) == n
+        if any(want):
+            trajs = [torch.empty((len(steps),) + tuple(p.shape), device=e0.device) if w else None for p, w in zip(poses, want)]
+            with torch.cuda.device(e0.device):
+                _check(e0.lib.cbd_sample_traj(n, hs, Bs, len(steps), steps, arr(poses), arr([z[0] for z in nz]), arr([z[1] for z in nz]),
+                                              arr([z[2] for z in nz]), arr(trajs), e0._stream()))
+            return trajs
         with torch.cuda.device(e0.device):
             _check(e0.lib.cbd_sample_multi(n, hs, Bs, len(steps), steps, arr(poses), arr([z[0] for z in nz]), arr([z[1] for z in nz]),
                                            arr([z[2] for z in nz]), e0._stream()))
@@ -452,7 +474,10 @@ class DockEnginePool:
         per = (B + self.n - 1) // self.n
         return [(lo, min(B, lo + per)) for lo in range(0, B, per)]
 
-    def sample(self, pos, steps, noise_tr=None, noise_rot=None, noise_tor=None):
+    def sample(self, pos, steps, noise_tr=None, noise_rot=None, noise_tor=None, trajectory=False):
+        if trajectory:
+            raise NotImplementedError("trajectory recording is not implemented for the multi-stream pool: use a single DockEngine "
+                                      "(DockEngine.sample / DockEngine.sample_multi)")
         B = pos.shape[0]
         if B > self.max_batch:
             raise RuntimeError(f"cbdock error -4: batch {B} exceeds max_batch {self.max_batch}")

@@ -448,9 +448,25 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     `n_streams` (extension): each batch is split over this many concurrent HIP streams (identical results).
     `co_schedule` (extension): when `data_list` holds poses of several complexes, up to this many (<= 8) complexes are advanced in
     lockstep with merged tensor-product launches (identical results; 1 = one complex at a time like the reference; default: as many
-    as bring a launch to ~160 poses)."""
+    as bring a launch to ~160 poses).
+    `return_full_trajectory`: returns (data_list, confidence, trajectory) like the reference (utils/sampling.py:267-268): trajectory[i]
+    is a CPU float32 tensor [inference_steps, Nl_i, 3], frame k the pose of data_list[i] after step k in the ligand-centred frame of
+    data["ligand"].pos (the last frame is the final pose).  The pose-update kernel records the frames on the device
+    (cbd_sample_traj) and they are downloaded once per co-scheduled wave.  With a `visualization_list` every frame is added as
+    add(frame + original_center, part=1, order=k + 2) -- what the reference's commented-out per-step add intended -- in place of the
+    single final order=2 frame.  Not implemented (NotImplementedError) for the host-stepped, non-default samplers: n_streams > 1,
+    SVGD and the score model's crop_beyond."""
     N = len(data_list)
-    assert not (return_full_trajectory or return_features or pivot), "Not implemented yet in new inference version"
+    assert not (return_features or pivot), "Not implemented yet in new inference version"
+    record = bool(return_full_trajectory)
+    if record:
+        svgd_on = svgd_weight_log_0 is not None and svgd_weight_log_1 is not None
+        why = ("n_streams > 1" if n_streams > 1 else "SVGD sampling" if svgd_on
+               else "the score model's crop_beyond" if getattr(model_args, "crop_beyond", None) is not None else None)
+        if why is not None:
+            raise NotImplementedError(f"return_full_trajectory is recorded by the one-launch step loop of a single engine; {why} "
+                                      "steps on the host or over several streams and does not record")
+    trajectory = [None] * N
     svgd = None
     if svgd_weight_log_0 is not None and svgd_weight_log_1 is not None:
         if ode or no_random:
@@ -621,11 +637,21 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
             for _, e, pos, nz, batch0, key in work:
                 _sample_cropped(e, _single_complex(batch0)[0], key, pos, steps, nz, float(score_crop))
         elif len(work) == 1:
-            work[0][1].sample(work[0][2], steps, *work[0][3])
+            t = work[0][1].sample(work[0][2], steps, *work[0][3], trajectory=record)
+            return [t] if record else None
         else:
-            DockEngine.sample_multi([w[1] for w in work], [w[2] for w in work], steps, [w[3] for w in work])
+            t = DockEngine.sample_multi([w[1] for w in work], [w[2] for w in work], steps, [w[3] for w in work], trajectory=record)
+            return t if record else None
 
-    def finish_wave(work):
+    def finish_wave(work, trajs=None):
+        if trajs is not None:          # one download for the wave: the groups' [S,b,Nl,3] blocks back to back
+            host = torch.cat([t.reshape(-1) for t in trajs]).cpu()
+            lo = 0
+            for (pend, _, pos, _, _, _), t in zip(work, trajs):
+                block = host[lo:lo + t.numel()].reshape(t.shape)
+                lo += t.numel()
+                for i in range(pos.shape[0]):
+                    trajectory[pend[0][0] + i] = block[:, i].clone()
         # Confidence of the wave's final poses: up to four complexes per set of fused-conv launches (cbd_conf_score_multi: a launch then
         # covers ~4x the waves and its last, partly filled round of resident waves costs ~1 % instead of ~6 %).  No host sync per
         # complex: the capacity flag of a confidence engine is sticky and checked once at the end.
@@ -670,9 +696,9 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
             groups.clear()
         work = prepare_wave(0) if waves else None
         for k in range(len(waves)):
-            launch_wave(work)
+            trajs = launch_wave(work)
             ahead = prepare_wave(k + 1) if plain and k + 1 < len(waves) else None
-            finish_wave(work)
+            finish_wave(work, trajs)
             work = ahead if ahead is not None else (prepare_wave(k + 1) if k + 1 < len(waves) else None)
 
     def drop_stale_capacity_flags(exc_type):
@@ -731,11 +757,15 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
         run_waves()
         if visualization_list is not None:
             for idx, visualization in enumerate(visualization_list):
-                visualization.add((data_list[idx]["ligand"].pos.detach().cpu() + data_list[idx].original_center.detach().cpu()),
-                                  part=1, order=2)
+                center = data_list[idx].original_center.detach().cpu()
+                if record:
+                    for t_idx in range(S):
+                        visualization.add(trajectory[idx][t_idx] + center, part=1, order=t_idx + 2)
+                else:
+                    visualization.add(data_list[idx]["ligand"].pos.detach().cpu() + center, part=1, order=2)
     if conf_model is not None:
         for ceng in conf_engines_used:
             ceng.check()          # raises if any of the batches above exceeded a per-atom edge capacity
         confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
-        return data_list, confidence
-    return data_list, None
+        return (data_list, confidence, trajectory) if record else (data_list, confidence)
+    return (data_list, None, trajectory) if record else (data_list, None)

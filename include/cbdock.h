@@ -131,6 +131,17 @@ int cbd_sample_multi(int32_t n, cbd_engine* const* engines, const int32_t* B, in
                      float* const* pos_dev, const float* const* noise_tr_dev, const float* const* noise_rot_dev,
                      const float* const* noise_tor_dev, void* stream);
 
+/* cbd_sample_multi that also records the pose after every step: traj_dev[k] is [S, B[k], Nl_k, 3] (device) or NULL;
+ * traj_dev itself may be NULL (then identical to cbd_sample_multi).  n = 1..8; n = 1 is cbd_sample without scores_out.
+ * Frame i of a batch is bitwise the pose that a call over steps 0..i alone returns, and frame S-1 is the returned pose: the pose
+ * update kernel stores each pose twice, there is no extra launch or copy per step.  Under "graph" the kernel writes into an
+ * engine-owned staging buffer ([S][max_batch][Nl][3] floats, allocated by the first recording call after cbd_set_complex) and one
+ * device-to-device copy per batch follows the graph launch.  Only this call records: every other entry point clears the
+ * engine's trajectory pointer before it launches, so a buffer may be freed as soon as the stream has passed this call. */
+int cbd_sample_traj(int32_t n, cbd_engine* const* engines, const int32_t* B, int32_t S, const cbd_step* steps_host,
+                    float* const* pos_dev, const float* const* noise_tr_dev, const float* const* noise_rot_dev,
+                    const float* const* noise_tor_dev, float* const* traj_dev, void* stream);
+
 /* Engine options.  "graph" (0/1): capture the S-step loop of cbd_sample into a hipGraph that is instantiated once per
  * (batch size, schedule) and replayed with one launch per batch (inputs are staged into engine-owned buffers).
  * "bf16" (0/1): run the two Linears of every tensor-product layer's radial MLP on bf16 matrix cores (bf16 operands, fp32
