@@ -565,7 +565,10 @@ hipError_t launch_bond_nb(const Multi& m, float lig_r, int cap, hipStream_t s) {
 // rigid update about the centroid, R sequential torsion rotations (utils/torsion.py:75-90, order dependent),
 // Kabsch re-alignment of the flexible pose onto the rigid one (utils/geometry.py:246-276; closed form via Horn's
 // quaternion + fp64 Jacobi, tests/test_kernel_math.py::horn_rotation).  One wave per sample, one lane per atom.
-// axis_angle_to_matrix, wave_sum, wave_sum_d: pose_math.h (shared with noise_transform.hip)
+// axis_angle_to_matrix, wave_sum, wave_sum_d: pose_math.h, shared with the other pose kernels.  This kernel's own: fp32 centroids, S
+// summed in fp64 from fp32 products, the rotation rounded to fp32, an fp32 final move -- and its own copy of the Horn matrix and Jacobi
+// sweeps of pose_math.h's horn_rotation: called through horn_rotation the sampled poses differ from this form in the last fp32 bit
+// (first seen at the second step of a 4-step trajectory of the tiny complex: 27.874016 here, 27.874014 shared); the cause is not found.
 __global__ __launch_bounds__(64) void pose_update_kernel(Multi mm, int step, SdeCoefs cf, int use_coefs, int with_torsion) {
   extern __shared__ float sp[];   // [Nl][3] flexible pose, [Nl][3] rigid pose
   int b;

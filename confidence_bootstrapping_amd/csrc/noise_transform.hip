@@ -7,7 +7,8 @@
 //         axis = flex[u] - flex[v];  the atoms of mask_rotate[r] turn by tor[r] about that axis through flex[v]
 //     out = flex moved rigidly onto `rigid` in the least-squares sense (Kabsch, utils/geometry.py:209-243);  R = 0 or no torsion: out = rigid
 // One wavefront per ligand, atoms strided over its lanes, both poses in LDS; the arithmetic is pose_update_kernel's (kernels.hip), with
-// the helpers of pose_math.h and the same Horn quaternion + fp64 Jacobi for the alignment (its centroids and last move in fp64 here).  The ragged description is CSR-like:
+// the helpers of pose_math.h: the quaternion route for the rotations and horn_rotation for the alignment.  This kernel's own: the
+// centroids of the alignment, S and the last move are fp64.  The ragged description is CSR-like:
 // lig_ptr / rot_ptr / mask_ptr are prefix sums over the ligands; mask_rotate is packed one bit per atom, ceil(Nl / 32) words per bond.
 // No atomics; every sum has a fixed order, so a ligand's result does not depend on the run nor on what shares the launch.
 #include <hip/hip_runtime.h>
@@ -50,16 +51,9 @@ __global__ __launch_bounds__(64) void noise_conformers_kernel(NoiseBatch nb) {
   const int* __restrict__ E = nb.rot_edge + (size_t)r0 * 2;
   const bool flexible = tor != nullptr && R > 0;
   const unsigned* __restrict__ M = flexible ? nb.mask_bits + nb.mask_ptr[p] : nullptr;
-  if (flexible) {   // bond ends must be atoms of this ligand: the torsion loop indexes LDS with them
-    bool good = true;
-    for (int r = lane; r < R; r += 64) {
-      const int u = E[2 * r], v = E[2 * r + 1];
-      good = good && u >= 0 && u < Nl && v >= 0 && v < Nl;
-    }
-    if (!__all(good)) {
-      for (int i = lane; i < 3 * Nl; i += 64) O[i] = __builtin_nanf("");
-      return;
-    }
+  if (flexible && !bond_ends_are_atoms(E, R, Nl, lane)) {   // the torsion loop indexes LDS with them
+    for (int i = lane; i < 3 * Nl; i += 64) O[i] = __builtin_nanf("");
+    return;
   }
   float* flex = sp;
   float* rigid = sp + 3 * Nl;
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(64) void noise_conformers_kernel(NoiseBatch nb) {
     __syncthreads();
     const unsigned* __restrict__ row = M + (size_t)rho * words;
     for (int a = lane; a < Nl; a += 64) {
-      if ((row[a >> 5] >> (a & 31)) & 1u) {
+      if (mask_bit(row, a)) {
         const float x = flex[3 * a] - vx, y = flex[3 * a + 1] - vy, z = flex[3 * a + 2] - vz;
         flex[3 * a] = Q[0] * x + Q[1] * y + Q[2] * z + vx;
         flex[3 * a + 1] = Q[3] * x + Q[4] * y + Q[5] * z + vy;
@@ -109,10 +103,9 @@ __global__ __launch_bounds__(64) void noise_conformers_kernel(NoiseBatch nb) {
   }
   // Kabsch: R, t minimising |R flex + t - rigid|  (the steps of pose_update_kernel; the two centroids and the final move are kept in
   // fp64 here -- a fp32 sum over up to 512 coordinates of tens of A would cost the output centroid more than the host path loses)
-  double fa[3] = {0, 0, 0}, fb[3] = {0, 0, 0};
-  for (int a = lane; a < Nl; a += 64)
-    for (int c = 0; c < 3; ++c) { fa[c] += (double)flex[3 * a + c]; fb[c] += (double)rigid[3 * a + c]; }
-  for (int c = 0; c < 3; ++c) { fa[c] = wave_sum_d(fa[c]) / (double)Nl; fb[c] = wave_sum_d(fb[c]) / (double)Nl; }
+  double fa[3], fb[3];
+  wave_centroid_d(flex, Nl, lane, fa);
+  wave_centroid_d(rigid, Nl, lane, fb);
   double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int a = lane; a < Nl; a += 64) {
     const double am[3] = {flex[3 * a] - fa[0], flex[3 * a + 1] - fa[1], flex[3 * a + 2] - fa[2]};
@@ -121,39 +114,8 @@ __global__ __launch_bounds__(64) void noise_conformers_kernel(NoiseBatch nb) {
       for (int k = 0; k < 3; ++k) S[3 * i + k] += am[i] * bm[k];
   }
   for (int i = 0; i < 9; ++i) S[i] = wave_sum_d(S[i]);
-  double N[4][4] = {{S[0] + S[4] + S[8], S[5] - S[7], S[6] - S[2], S[1] - S[3]},
-                    {S[5] - S[7], S[0] - S[4] - S[8], S[1] + S[3], S[6] + S[2]},
-                    {S[6] - S[2], S[1] + S[3], -S[0] + S[4] - S[8], S[5] + S[7]},
-                    {S[1] - S[3], S[6] + S[2], S[5] + S[7], -S[0] - S[4] + S[8]}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    for (int pp = 0; pp < 3; ++pp)
-      for (int q = pp + 1; q < 4; ++q) {
-        const double apq = N[pp][q];
-        if (fabs(apq) < 1e-280) continue;
-        const double th = (N[q][q] - N[pp][pp]) / (2.0 * apq);
-        const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {   // N <- N J
-          const double nkp = N[k][pp], nkq = N[k][q];
-          N[k][pp] = c * nkp - s * nkq; N[k][q] = s * nkp + c * nkq;
-        }
-        for (int k = 0; k < 4; ++k) {   // N <- J^T N
-          const double npk = N[pp][k], nqk = N[q][k];
-          N[pp][k] = c * npk - s * nqk; N[q][k] = s * npk + c * nqk;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k][pp], vkq = V[k][q];
-          V[k][pp] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int best = 0;
-  for (int k = 1; k < 4; ++k) if (N[k][k] > N[best][best]) best = k;
-  const double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
-  const double Rk[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
-                        2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
-                        2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z};
+  double Rk[9];
+  horn_rotation(S, Rk);
   // aligned = R (flex - ca) + cb
   for (int a = lane; a < Nl; a += 64) {
     const double fx = flex[3 * a] - fa[0], fy = flex[3 * a + 1] - fa[1], fz = flex[3 * a + 2] - fa[2];

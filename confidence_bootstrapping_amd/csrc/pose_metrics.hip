@@ -48,14 +48,6 @@ CBD_DEV double wave_min_d(double v) {
   return v;
 }
 
-// centroid of n atoms in LDS, the same value in every lane
-CBD_DEV void wave_centroid_d(const float* __restrict__ x, int n, int lane, double (&c)[3]) {
-  c[0] = c[1] = c[2] = 0.0;
-  for (int a = lane; a < n; a += 64)
-    for (int k = 0; k < 3; ++k) c[k] += (double)x[3 * a + k];
-  for (int k = 0; k < 3; ++k) c[k] = wave_sum_d(c[k]) / (double)n;
-}
-
 // grid: P workgroups of four waves; dynamic LDS: (max_n + max_ref) * 3 floats
 __global__ __launch_bounds__(256) void pose_metrics_kernel(PoseMetricsBatch b) {
   extern __shared__ float coords[];   // pose [max_n][3], then the complex's crystal poses [Q][N][3]

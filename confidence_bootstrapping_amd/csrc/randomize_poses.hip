@@ -11,7 +11,7 @@
 // with the atoms are fp64 and round to fp32 once per bond -- what the host path does with scipy / numpy, and what its deviation from
 // fp64, the yardstick of tests/test_gpu_randomize_batch.py, is made of.  The fp32 quaternion route of pose_math.h was NOT tried against
 // that bound: fp64 was chosen up front, on the estimate that fp32 matrix entries (a few 1e-7 relative) times the lever of a far atom
-// come close to it; at one matrix per bond the cost is nothing.  The centroid (wave_sum_d) and the last move are fp64 as well and round once.
+// come close to it; at one matrix per bond the cost is nothing.  The centroid (wave_centroid_d) and the last move are fp64 as well and round once.
 // No atomics; every sum has a fixed order, so a pose's result depends neither on the run nor on what shares the launch.
 #include <hip/hip_runtime.h>
 
@@ -75,14 +75,7 @@ __global__ __launch_bounds__(64) void randomize_poses_kernel(RandomizeBatch rb) 
   }
   const bool flexible = with_tor && R > 0;
   const int* __restrict__ E = flexible ? rb.rot_edge + (size_t)r0 * 2 : nullptr;
-  if (good && flexible) {   // bond ends must be atoms of this ligand: the torsion loop indexes LDS with them
-    bool in = true;
-    for (int r = lane; r < R; r += 64) {
-      const int u = E[2 * r], v = E[2 * r + 1];
-      in = in && u >= 0 && u < Nl && v >= 0 && v < Nl;
-    }
-    good = __all(in);
-  }
+  if (good && flexible) good = bond_ends_are_atoms(E, R, Nl, lane);   // the torsion loop indexes LDS with them
   if (!good) {   // an index that names no ligand / complex, sizes that contradict each other, a bond end that is no atom: NaN, nothing indexed with it
     for (int i = lane; i < 3 * No; i += 64) O[i] = __builtin_nanf("");
     return;
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(64) void randomize_poses_kernel(RandomizeBatch rb) 
       __syncthreads();
       const unsigned* __restrict__ row = M + (size_t)rho * words;
       for (int a = lane; a < Nl; a += 64) {
-        if ((row[a >> 5] >> (a & 31)) & 1u) {
+        if (mask_bit(row, a)) {
           const double x = (double)flex[3 * a] - vx, y = (double)flex[3 * a + 1] - vy, z = (double)flex[3 * a + 2] - vz;
           flex[3 * a] = (float)(Q[0] * x + Q[1] * y + Q[2] * z + vx);
           flex[3 * a + 1] = (float)(Q[3] * x + Q[4] * y + Q[5] * z + vy);
@@ -117,10 +110,8 @@ __global__ __launch_bounds__(64) void randomize_poses_kernel(RandomizeBatch rb) 
       __syncthreads();
     }
   }
-  double c[3] = {0, 0, 0};
-  for (int a = lane; a < Nl; a += 64)
-    for (int k = 0; k < 3; ++k) c[k] += (double)flex[3 * a + k];
-  for (int k = 0; k < 3; ++k) c[k] = wave_sum_d(c[k]) / (double)Nl;
+  double c[3];
+  wave_centroid_d(flex, Nl, lane, c);
   double Rm[9], t[3];
   for (int k = 0; k < 9; ++k) Rm[k] = (double)rb.rot_mat[(size_t)p * 9 + k];
   for (int k = 0; k < 3; ++k) t[k] = (double)rb.center[(size_t)cx * 3 + k] + (rb.tr ? (double)rb.tr[(size_t)p * 3 + k] : 0.0);

@@ -4,9 +4,9 @@
 //     f(theta) = min over rigid motions of RMSD(probe with its R dihedrals SET to theta, target).
 // Every torsion bond is a bridge, so the dihedrals are independent: the probe's own dihedral phi_r is computed once and the rotating side
 // of bond r (mask_rotate row r) is turned by +-(theta_r - phi_r) about the bond axis, r = 0 .. R-1 in order, with the rotation arithmetic
-// of pose_update_kernel (kernels.hip; restated here so that that kernel stays bitwise what it is).  The aligned RMSD is closed form:
+// of pose_update_kernel (kernels.hip; axis_angle_to_matrix of pose_math.h).  The aligned RMSD is closed form:
 // rmsd^2 = (sum|a|^2 + sum|b|^2 - 2 lambda_max) / Nl on centred coordinates, lambda_max = the largest eigenvalue of Horn's 4x4 matrix
-// (fp64 Jacobi).  Dihedral convention: IUPAC / rdkit -- cis 0, trans pi, looking down u -> v a clockwise turn of l relative to k is positive.
+// (horn_lambda_max of pose_math.h: fp64 Jacobi without eigenvectors).  Dihedral convention: IUPAC / rdkit -- cis 0, trans pi, looking down u -> v a clockwise turn of l relative to k is positive.
 //
 // match_score_kernel: f for given theta vectors, one wave per (problem, theta), one lane per atom (strided for Nl > 64).
 // match_de_kernel:    the whole differential evolution of one problem in one workgroup of 4 waves, population / trials / fitness in LDS,
@@ -22,6 +22,7 @@
 
 #include "device_util.h"
 #include "host_util.h"
+#include "pose_math.h"
 
 namespace cbd {
 
@@ -52,62 +53,6 @@ struct DeParams {
   float* fitness_out;             // [n]
   int* gens_out;                  // [n]
 };
-
-CBD_DEV void tm_axis_angle_to_matrix(float ax, float ay, float az, float (&R)[9]) {
-  // via quaternion, incl. the |angle| < 1e-6 series branch (utils/geometry.py:39-86); the code of pose_update_kernel
-  const float ang = sqrtf(ax * ax + ay * ay + az * az);
-  const float half = 0.5f * ang;
-  const float k = fabsf(ang) < 1e-6f ? 0.5f - (ang * ang) / 48.f : sinf(half) / ang;
-  const float r = cosf(half), i = ax * k, j = ay * k, kk = az * k;
-  const float two_s = 2.0f / (r * r + i * i + j * j + kk * kk);
-  R[0] = 1 - two_s * (j * j + kk * kk); R[1] = two_s * (i * j - kk * r);     R[2] = two_s * (i * kk + j * r);
-  R[3] = two_s * (i * j + kk * r);     R[4] = 1 - two_s * (i * i + kk * kk); R[5] = two_s * (j * kk - i * r);
-  R[6] = two_s * (i * kk - j * r);     R[7] = two_s * (j * kk + i * r);     R[8] = 1 - two_s * (i * i + j * j);
-}
-
-CBD_DEV float tm_wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-CBD_DEV double tm_wave_sum_d(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// largest eigenvalue of Horn's symmetric 4x4 matrix built from S = sum a b^T: cyclic Jacobi in fp64 (the sweeps of pose_update_kernel
-// without the eigenvectors; stops once the off-diagonal part is below fp64 resolution of the diagonal)
-CBD_DEV double horn_lambda_max(const double (&S)[9]) {
-  double N[4][4] = {{S[0] + S[4] + S[8], S[5] - S[7], S[6] - S[2], S[1] - S[3]},
-                    {S[5] - S[7], S[0] - S[4] - S[8], S[1] + S[3], S[6] + S[2]},
-                    {S[6] - S[2], S[1] + S[3], -S[0] + S[4] - S[8], S[5] + S[7]},
-                    {S[1] - S[3], S[6] + S[2], S[5] + S[7], -S[0] - S[4] + S[8]}};
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    const double off = fabs(N[0][1]) + fabs(N[0][2]) + fabs(N[0][3]) + fabs(N[1][2]) + fabs(N[1][3]) + fabs(N[2][3]);
-    const double dia = fabs(N[0][0]) + fabs(N[1][1]) + fabs(N[2][2]) + fabs(N[3][3]);
-    if (off <= 1e-18 * dia) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = N[p][q];
-        if (fabs(apq) < 1e-280) continue;
-        const double th = (N[q][q] - N[p][p]) / (2.0 * apq);
-        const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // N <- N J
-          const double nkp = N[k][p], nkq = N[k][q];
-          N[k][p] = c * nkp - s * nkq; N[k][q] = s * nkp + c * nkq;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // N <- J^T N
-          const double npk = N[p][k], nqk = N[q][k];
-          N[p][k] = c * npk - s * nqk; N[q][k] = s * npk + c * nqk;
-        }
-      }
-  }
-  return fmax(fmax(N[0][0], N[1][1]), fmax(N[2][2], N[3][3]));
-}
 
 // IUPAC dihedral of four points
 CBD_DEV float dihedral4(const float* p0, const float* p1, const float* p2, const float* p3) {
@@ -187,7 +132,7 @@ struct WaveProblem {
         rot[s] = m;
       }
     }
-    cx = tm_wave_sum(cx) / (float)nl; cy = tm_wave_sum(cy) / (float)nl; cz = tm_wave_sum(cz) / (float)nl;
+    cx = wave_sum(cx) / (float)nl; cy = wave_sum(cy) / (float)nl; cz = wave_sum(cz) / (float)nl;
     double b2 = 0.0;
 #pragma unroll
     for (int s = 0; s < TM_SLOTS; ++s) {
@@ -196,7 +141,7 @@ struct WaveProblem {
         b2 += (double)tx[s] * tx[s] + (double)ty[s] * ty[s] + (double)tz[s] * tz[s];
       }
     }
-    tb2 = tm_wave_sum_d(b2);
+    tb2 = wave_sum_d(b2);
     return true;
   }
 
@@ -217,7 +162,7 @@ struct WaveProblem {
       const float n = sqrtf(ax * ax + ay * ay + az * az);
       ax = ax / n * th; ay = ay / n * th; az = az / n * th;
       float Q[9];
-      tm_axis_angle_to_matrix(ax, ay, az, Q);
+      axis_angle_to_matrix(ax, ay, az, Q);
 #pragma unroll
       for (int s = 0; s < TM_SLOTS; ++s) {
         if ((rot[s] >> r) & 1u) {
@@ -232,7 +177,7 @@ struct WaveProblem {
 #pragma unroll
     for (int s = 0; s < TM_SLOTS; ++s)
       if (lane + 64 * s < nl) { cx += x[s]; cy += y[s]; cz += z[s]; }
-    cx = tm_wave_sum(cx) / (float)nl; cy = tm_wave_sum(cy) / (float)nl; cz = tm_wave_sum(cz) / (float)nl;
+    cx = wave_sum(cx) / (float)nl; cy = wave_sum(cy) / (float)nl; cz = wave_sum(cz) / (float)nl;
     double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     double a2 = 0.0;
 #pragma unroll
@@ -249,8 +194,8 @@ struct WaveProblem {
       }
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) S[i] = tm_wave_sum_d(S[i]);
-    a2 = tm_wave_sum_d(a2);
+    for (int i = 0; i < 9; ++i) S[i] = wave_sum_d(S[i]);
+    a2 = wave_sum_d(a2);
     const double lam = horn_lambda_max(S);
     const double r2 = (a2 + tb2 - 2.0 * lam) / (double)nl;
     return (float)sqrt(fmax(r2, 0.0));
@@ -325,13 +270,13 @@ CBD_DEV void de_stats(const float* fit, int P, float tol, int* s_stat) {
     const unsigned long long w = __shfl_xor(best, o);
     best = w < best ? w : best;
   }
-  const double mean = tm_wave_sum_d(sum) / (double)P;
+  const double mean = wave_sum_d(sum) / (double)P;
   double var = 0.0;
   for (int i = lane; i < P; i += 64) {
     const double d = (double)fit[i] - mean;
     var += d * d;
   }
-  var = tm_wave_sum_d(var) / (double)P;
+  var = wave_sum_d(var) / (double)P;
   if (lane == 0) {
     s_stat[0] = (int)(best & 0xffffffffu);
     s_stat[1] = sqrt(var) <= (double)tol * fabs(mean) ? 1 : 0;

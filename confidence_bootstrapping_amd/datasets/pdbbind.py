@@ -186,7 +186,7 @@ class NoiseTransform:
         ragged batch, ONE cbd_noise_conformers launch on the current stream; every item's `['ligand'].pos` is then its slice of the
         device output (fp32, on `device`).  An item over the kernel's capacity (Nl > 512 or R > 128) is moved by the host
         `modify_conformer` and stays on the host.  There is no CPU path: `device` must be a GPU.  -> data_list"""
-        from .. import engine
+        from .. import engine, staging
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("apply_noise_batch moves the poses on the MI355X (cbd_noise_conformers); use __call__ per item on the host")
@@ -201,30 +201,19 @@ class NoiseTransform:
                 fit.append((d, tr_u, rot_u, tor_u, nl, n_tor) + self._packed(d))
         if not fit:
             return data_list
-        n = len(fit)
         nls, rs = np.asarray([f[4] for f in fit], dtype=np.int64), np.asarray([f[5] for f in fit], dtype=np.int64)
-        ptr = lambda sizes: np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-        lig_ptr, rot_ptr, mask_ptr = ptr(nls), ptr(rs), ptr(rs * ((nls + 31) // 32))
-        with_tor = not self.no_torsion
-        # one staging buffer of 4-byte words: the three prefix sums, the bond ends, the packed masks, then the float32 parts
-        parts = [lig_ptr, rot_ptr, mask_ptr,
-                 np.concatenate([f[6].reshape(-1) for f in fit]), np.concatenate([f[7].reshape(-1) for f in fit]).view(np.int32),
-                 np.concatenate([f[0]["ligand"].pos.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1) for f in fit]).view(np.int32),
-                 np.concatenate([f[1].numpy().astype(np.float32, copy=False).reshape(-1) for f in fit]).view(np.int32),
-                 np.concatenate([np.asarray(f[2], dtype=np.float32).reshape(-1) for f in fit]).view(np.int32),
-                 (np.concatenate([np.asarray(f[3], dtype=np.float32).reshape(-1) for f in fit]) if with_tor else np.zeros(0, np.float32)).view(np.int32)]
-        offs = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
-        host = torch.empty(int(offs[-1]), dtype=torch.int32, pin_memory=True)
-        np.concatenate(parts, out=host.numpy())
+        lig_ptr = staging.ptr(nls)
+        f32 = lambda arrays: np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in arrays])
+        staged, at = staging.upload(dict(
+            lig_ptr=lig_ptr, rot_ptr=staging.ptr(rs), mask_ptr=staging.ptr(rs * ((nls + 31) // 32)),
+            rot_edge=np.concatenate([f[6].reshape(-1) for f in fit]), mask_bits=np.concatenate([f[7].reshape(-1) for f in fit]),
+            pos_in=f32(f[0]["ligand"].pos.detach().cpu().numpy() for f in fit), tr=f32(f[1].numpy() for f in fit),
+            rot=f32(f[2] for f in fit), tor=None if self.no_torsion else f32(f[3] for f in fit)), dev)
         with torch.cuda.device(dev):
-            staged = host.to(dev, non_blocking=True)
             out = torch.empty(int(lig_ptr[-1]), 3, dtype=torch.float32, device=dev)
-            at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k])) if offs[k + 1] > offs[k] else None    # part k, NULL when empty
-            rc = lib.cbd_noise_conformers(n, int(nls.max()), int(rs.max()), at(0), at(5), at(1), at(3), at(2), at(4), at(6), at(7),
-                                          at(8) if with_tor else None, C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
+            engine._check(lib.cbd_noise_conformers(len(fit), int(nls.max()), int(rs.max()), at("lig_ptr"), at("pos_in"), at("rot_ptr"),
+                                                   at("rot_edge"), at("mask_ptr"), at("mask_bits"), at("tr"), at("rot"), at("tor"),
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         # `staged` is read by the kernel just enqueued on the stream it was allocated on: the caching allocator orders its reuse behind it
         for f, a0, a1 in zip(fit, lig_ptr[:-1], lig_ptr[1:]):
             f[0]["ligand"].pos = out[int(a0):int(a1)]

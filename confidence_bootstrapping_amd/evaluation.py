@@ -81,7 +81,7 @@ def _pack_pose_metrics(prepared):
     in order.  -> dict: pose_cplx [P], pose_ptr [P + 1], cplx_n, cplx_k, cplx_q [C], ref_ptr [C + 1] (int32; the ptr arrays count
     atoms), pos float32 [sum N over poses, 3], ref float32 [sum Q N, 3], idx_ref / idx_pos (lists of the C host tables [K, N]), max_n,
     max_ref."""
-    ptr = lambda sizes: np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int32)
+    from .staging import ptr
     cat = lambda arrays: np.concatenate([a.reshape(-1, 3) for a in arrays]) if arrays else np.zeros((0, 3), dtype=np.float32)
     return dict(
         pose_cplx=np.asarray([c for c, it in enumerate(prepared) for _ in range(it["P"])], dtype=np.int32),
@@ -110,7 +110,7 @@ def pose_metrics_batch(items, device, isomorphisms=None):
     in the last bit).  An item over the kernel's capacity (N > 512 or Q * N > 4096) takes the host route (pose_metrics).  `isomorphisms`:
     optional list with one (idx1, idx2) or None per item, used as given (not cached).  There is no CPU path: `device` must be a GPU."""
     import ctypes as C
-    from . import engine, molecules_utils as mu
+    from . import engine, staging, molecules_utils as mu
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("pose_metrics_batch measures the poses on the MI355X (cbd_pose_metrics); use pose_metrics on the host")
@@ -125,24 +125,17 @@ def pose_metrics_batch(items, device, isomorphisms=None):
     n_poses = len(pk["pose_cplx"])
     with torch.cuda.device(dev):
         tables = [mu._iso_device_tables(it["key"], it["entry"], dev) for it in fit]      # resident; uploaded only when first seen
-        pk["idx_ref_tab"] = np.asarray([t[0].data_ptr() for t in tables], dtype=np.uint64)
-        pk["idx_pos_tab"] = np.asarray([t[1].data_ptr() for t in tables], dtype=np.uint64)
-        # one staging buffer of 4-byte words; the 8-byte pointer tables come first, so that they are aligned on both sides
-        names = ("idx_ref_tab", "idx_pos_tab", "pose_cplx", "pose_ptr", "cplx_n", "cplx_k", "cplx_q", "ref_ptr", "pos", "ref")
-        parts = [np.ascontiguousarray(pk[k]).reshape(-1).view(np.int32) for k in names]
-        offs = dict(zip(names, np.concatenate([[0], np.cumsum([len(p) for p in parts])[:-1]])))
-        host = torch.empty(sum(len(p) for p in parts), dtype=torch.int32, pin_memory=True)
-        np.concatenate(parts, out=host.numpy())
-        staged = host.to(dev, non_blocking=True)
+        staged, at = staging.upload(dict(
+            {k: pk[k] for k in ("pose_cplx", "pose_ptr", "cplx_n", "cplx_k", "cplx_q", "ref_ptr", "pos", "ref")},
+            idx_ref_tab=np.asarray([t[0].data_ptr() for t in tables], dtype=np.uint64),
+            idx_pos_tab=np.asarray([t[1].data_ptr() for t in tables], dtype=np.uint64)), dev)
         out = torch.empty(5, n_poses, dtype=torch.int32, device=dev)      # rmsd, centroid, min_self (fp32 bits), argmin_ref, argmin_iso
-        at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k]))
         row = lambda r: C.c_void_p(out.data_ptr() + 4 * r * n_poses)
-        rc = lib.cbd_pose_metrics(n_poses, len(fit), int(pk["max_n"]), int(pk["max_ref"]), at("pose_cplx"), at("pose_ptr"), at("pos"),
-                                  at("cplx_n"), at("cplx_k"), at("cplx_q"), at("ref_ptr"), at("ref"), at("idx_ref_tab"), at("idx_pos_tab"),
-                                  row(0), row(1), row(2), row(3), row(4), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
-        got = out.cpu().numpy()      # the one download; it also orders `staged`, `host` and the index tables behind the kernel
+        engine._check(lib.cbd_pose_metrics(
+            n_poses, len(fit), int(pk["max_n"]), int(pk["max_ref"]), at("pose_cplx"), at("pose_ptr"), at("pos"), at("cplx_n"), at("cplx_k"),
+            at("cplx_q"), at("ref_ptr"), at("ref"), at("idx_ref_tab"), at("idx_pos_tab"), row(0), row(1), row(2), row(3), row(4),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        got = out.cpu().numpy()      # the one download; it also orders `staged` and the index tables behind the kernel
     f32, p0 = got[:3].view(np.float32), 0
     fit_ids = [i for i, r in enumerate(results) if r is None]
     for i, it in zip(fit_ids, fit):

@@ -148,6 +148,7 @@ def _pack_randomization(groups, centers, draws):
     mask_bits uint32 (flat); pos_in float32 [sum Nl, 3]; tor float64 [sum R over poses] or None; rot_mat float32 [P, 9]; tr float32
     [P, 3] or None; center float32 [C, 3]; max_nl, max_r."""
     from .datasets.pdbbind import pack_ligand
+    from .staging import ptr
     pose_lig, pose_cplx, nl_of, r_of, descs = [], [], [], [], []
     for c, group in enumerate(groups):
         first = len(descs)                   # the description of the group's first graph
@@ -161,7 +162,6 @@ def _pack_randomization(groups, centers, draws):
             pose_cplx.append(c)
             nl_of.append(descs[lig][0].shape[0])
             r_of.append(descs[lig][1].shape[0])
-    ptr = lambda sizes: np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int32)
 
     def cat(arrays, dtype, shape):
         arrays = [np.asarray(a, dtype=dtype).reshape(shape) for a in arrays]
@@ -187,7 +187,7 @@ def randomize_position_batch(groups, no_torsion, no_random, tr_sigma_max, device
     `['ligand'].pos` is then an fp32 CPU tensor of its old shape.  A group with a ligand over the kernel's capacity (Nl > 512 or
     R > 128) is moved on the host with the draws already made.  There is no CPU path: `device` must be a GPU.  No reference counterpart."""
     import ctypes as C
-    from . import engine
+    from . import engine, staging
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("randomize_position_batch moves the poses on the MI355X (cbd_randomize_poses); use randomize_position on the host")
@@ -205,25 +205,14 @@ def randomize_position_batch(groups, no_torsion, no_random, tr_sigma_max, device
     if not fit:
         return groups
     pk = _pack_randomization(fit, centers, draws)
-    # one staging buffer of 4-byte words; the fp64 torsion updates come first, so that they are 8-byte aligned on both sides
-    names = ("tor", "pose_lig", "pose_cplx", "out_ptr", "tor_ptr", "lig_ptr", "rot_ptr", "mask_ptr", "rot_edge", "mask_bits", "pos_in",
-             "rot_mat", "tr", "center")
-    parts = [(np.zeros(0, np.int32) if pk[k] is None else np.ascontiguousarray(pk[k]).reshape(-1).view(np.int32)) for k in names]
-    offs = dict(zip(names, np.concatenate([[0], np.cumsum([len(p) for p in parts])[:-1]])))
-    host = torch.empty(sum(len(p) for p in parts), dtype=torch.int32, pin_memory=True)
-    np.concatenate(parts, out=host.numpy())
-    n_atoms = int(pk["out_ptr"][-1])
+    staged, at = staging.upload({k: v for k, v in pk.items() if k not in ("max_nl", "max_r")}, dev)
     with torch.cuda.device(dev):
-        staged = host.to(dev, non_blocking=True)
-        out = torch.empty(n_atoms, 3, dtype=torch.float32, device=dev)
-        at = lambda k: C.c_void_p(staged.data_ptr() + 4 * int(offs[k])) if pk[k] is not None and pk[k].size else None    # NULL when empty
-        rc = lib.cbd_randomize_poses(len(pk["pose_lig"]), len(pk["lig_ptr"]) - 1, len(fit), int(pk["max_nl"]), int(pk["max_r"]),
-                                     at("pose_lig"), at("pose_cplx"), at("out_ptr"), at("tor_ptr"), at("lig_ptr"), at("pos_in"),
-                                     at("rot_ptr"), at("rot_edge"), at("mask_ptr"), at("mask_bits"), at("tor"), at("rot_mat"), at("tr"),
-                                     at("center"), C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cbdock error {rc}: {lib.cbd_last_error().decode()}")
-        moved = out.cpu()      # the one download; it also orders `staged` and `host` behind the kernel
+        out = torch.empty(int(pk["out_ptr"][-1]), 3, dtype=torch.float32, device=dev)
+        engine._check(lib.cbd_randomize_poses(
+            len(pk["pose_lig"]), len(pk["lig_ptr"]) - 1, len(fit), int(pk["max_nl"]), int(pk["max_r"]), at("pose_lig"), at("pose_cplx"),
+            at("out_ptr"), at("tor_ptr"), at("lig_ptr"), at("pos_in"), at("rot_ptr"), at("rot_edge"), at("mask_ptr"), at("mask_bits"), at("tor"),
+            at("rot_mat"), at("tr"), at("center"), C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        moved = out.cpu()      # the one download; it also orders `staged` behind the kernel
     graphs = [g for group in fit for g in group]
     for g, a0, a1 in zip(graphs, pk["out_ptr"][:-1], pk["out_ptr"][1:]):
         g["ligand"].pos = moved[int(a0):int(a1)].clone()
