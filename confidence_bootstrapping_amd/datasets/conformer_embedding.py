@@ -15,9 +15,13 @@ Deviations from the reference's ETKDG, all deliberate:
   * hydrogens are NOT added.  The reference embeds `AddHs(mol)` and strips them again; here the atoms are used as given (heavy atoms
     after `remove_hs`, or with the explicit hydrogens of the file).  Heavy-atom geometry is fixed by the 1-2 / 1-3 / 1-4 bounds alike.
   * no torsion preferences and no metric-matrix eigen-embedding (random start coordinates only).
-  * stereo comes from a 3-D input pose (`ref_pos`) only: the sign of every sp3 centre's neighbour volume, and the cis / trans side of
-    double and amide bonds, are read from it.  A flat or missing `ref_pos` gives no sign constraints (the centres are still kept
-    from flattening, with either hand) and leaves double / amide bonds their whole cis..trans range.
+  * stereo comes from a 3-D input pose (`ref_pos`; `stereo="pose"`, the default): the sign of every sp3 centre's neighbour volume,
+    and the cis / trans side of double and amide bonds, are read from it.  A flat or missing `ref_pos` gives no sign constraints (the
+    centres are still kept from flattening, with either hand) and leaves double / amide bonds their whole cis..trans range.
+    A molecule without a pose -- one read from a SMILES (datasets/smiles.py) -- carries its stereo on itself: `stereo="tags"` takes
+    the sign of a centre's volume from its `chiral_tag` and the side of a double bond from `mol.double_bond_stereo`; a centre without
+    a tag and a double bond without a record get what a missing pose gives.  Amide bonds have no record: an unflagged amide may
+    come out cis, where ETKDG's torsion preferences would make it trans.
   * at most 256 atoms.
 
 Sources of the tables: covalent radii -- Cordero et al., Dalton Trans. 2008; typical bond lengths by class -- Allen et al., J. Chem.
@@ -239,12 +243,16 @@ def centre_volume(p, quad):
     return float(np.dot(n1 - c, np.cross(n2 - c, n3 - c)))
 
 
-def distance_bounds(mol, ref_pos=None):
+def distance_bounds(mol, ref_pos=None, stereo="pose"):
     """-> (lower [N, N], upper [N, N], constraints) of a perceived `molfile.Mol`, float64, triangle-smoothed.
 
     The atoms are used as given -- heavy atoms after `remove_hs`, or with the file's explicit hydrogens; hydrogens are NOT added the
     way the reference's `AddHs` does (see the module text).  `ref_pos` [N, 3]: a 3-D pose that stereo is read from (the sign of each
     sp3 centre's volume; the cis / trans side of double and amide bonds).  A flat or missing `ref_pos` gives no sign constraints.
+    `stereo`: "pose" -- stereo from `ref_pos` as just described; "tags" -- from the molecule: the sign of a centre's volume from its
+    `chiral_tag` (CHI_TETRAHEDRAL_CCW: the first three neighbours in bond order span a positive volume), the cis / trans side of a
+    double bond's 1-4 pairs from `mol.double_bond_stereo`; `ref_pos` is then not looked at, and an untagged centre or an unrecorded
+    double bond gets what "pose" gives without a pose.
 
     `constraints` = dict(idx int32 [nc, 4], lo / hi float64 [nc], kind int32 [nc]):
       KIND_VOLUME      V = (n1 - c) . ((n2 - c) x (n3 - c)) of (c, n1, n2, n3), the first three listed neighbours of the sp3 centre c,
@@ -261,8 +269,16 @@ def distance_bounds(mol, ref_pos=None):
     for a in mol.atoms:
         if a.z not in _COVALENT:
             raise ValueError(f"element {a.symbol} is outside the organic subset the bond-length table covers")
+    if stereo not in ("pose", "tags"):
+        raise ValueError(f"stereo={stereo!r}: \"pose\" or \"tags\"")
+    tags = stereo == "tags"
+    side = {}                                # (b, c) -> (a, d, cis?) for the recorded double bonds, both directions
+    if tags:
+        for a_, b_, c_, d_, rel in getattr(mol, "double_bond_stereo", ()):
+            side[(b_, c_)], side[(c_, b_)] = (a_, d_, rel == "cis"), (d_, a_, rel == "cis")
+    tag_sign = lambda c: {"CHI_TETRAHEDRAL_CCW": 1, "CHI_TETRAHEDRAL_CW": -1}.get(mol.atoms[c].chiral_tag, 0) if tags else 0
     ref = None
-    if ref_pos is not None:
+    if ref_pos is not None and not tags:
         ref = np.asarray(ref_pos, dtype=np.float64)
         if ref.shape != (n, 3):
             raise ValueError(f"ref_pos {ref.shape} is not [{n}, 3]")
@@ -352,6 +368,10 @@ def distance_bounds(mol, ref_pos=None):
                 elif flat_bond and not shared and ref is not None:
                     v = cis if abs(_torsion(ref, i, j, k, l)) < 0.5 * math.pi else trans
                     lo, up = v - GEN_TOL - soft, v + GEN_TOL + soft
+                elif cls == "D" and not shared and (j, k) in side:
+                    a_, d_, same_side = side[(j, k)]              # the other substituent of an end lies on the other side
+                    v = cis if same_side == ((i == a_) == (l == d_)) else trans
+                    lo, up = v - GEN_TOL - soft, v + GEN_TOL + soft
                 put(i, l, lo, up, 3)
     # everything further apart: van-der-Waals lower bounds by topological distance
     topo = np.full((n, n), 99, dtype=np.int64)
@@ -393,7 +413,7 @@ def distance_bounds(mol, ref_pos=None):
                              [r[0] * r[1] * cosines[0], r[1] ** 2, r[1] * r[2] * cosines[2]],
                              [r[0] * r[2] * cosines[1], r[1] * r[2] * cosines[2], r[2] ** 2]])
             ideal = math.sqrt(max(float(np.linalg.det(gram)), 0.0))
-            sign = 0
+            sign = tag_sign(c)
             if ref is not None:
                 v = centre_volume(ref, q)
                 if abs(v) > 0.25 * ideal:
@@ -409,7 +429,7 @@ def distance_bounds(mol, ref_pos=None):
                     for y in range(4):
                         cm[1 + x, 1 + y] = 0.0 if x == y else d13[(t[x], c, t[y])] ** 2
                 ideal4 = math.sqrt(max(float(np.linalg.det(cm)) / 288.0, 0.0)) * 6.0
-                sign4 = 0
+                sign4 = tag_sign(c)      # the centre lies inside its neighbours' tetrahedron: both volumes have one sign
                 if ref is not None:
                     v = centre_volume(ref, t)
                     if abs(v) > 0.25 * ideal4:
@@ -533,19 +553,19 @@ def embed_conformers_batch(items, n, seed=0, device=None, conf_ids=None, mol_ids
     return out
 
 
-def embed_conformers(mol, n, seed=0, ref_pos=None, device=None, conf_ids=None, mol_id=0, iters=DEFAULT_ITERS):
+def embed_conformers(mol, n, seed=0, ref_pos=None, device=None, conf_ids=None, mol_id=0, iters=DEFAULT_ITERS, stereo="pose"):
     """n conformers of one perceived molecule -> (pos [n, N, 3] float64, ok [n] bool, error [n] float64).  `ok`: the conformer
     passes the acceptance test (every pair distance within BOUND_TOL of its bounds, every sp3 centre with the hand of `ref_pos` and
     not flattened, every sp2 centre and aromatic ring atom planar within PLANAR_LIMIT); `error`: the final value of the objective.
-    The same (seed, mol_id, conformer id) gives bitwise the same coordinates in any launch."""
-    return embed_conformers_batch([(mol, ref_pos)], n, seed=seed, device=device, conf_ids=None if conf_ids is None else [conf_ids],
+    The same (seed, mol_id, conformer id) gives bitwise the same coordinates in any launch.  `stereo`: see `distance_bounds`."""
+    return embed_conformers_batch([distance_bounds(mol, ref_pos, stereo=stereo)], n, seed=seed, device=device, conf_ids=None if conf_ids is None else [conf_ids],
                                   mol_ids=[mol_id], iters=iters)[0]
 
 
-def embed_until_ok(mol, n, seed=0, ref_pos=None, device=None, rounds=3):
+def embed_until_ok(mol, n, seed=0, ref_pos=None, device=None, rounds=3, stereo="pose"):
     """n conformers, each not-ok one replaced from further conformer ids (at most `rounds` more launches); what is still not ok after
     that stays as the least-violating candidate seen.  -> (pos [n, N, 3], ok [n], error [n])."""
-    bounds = distance_bounds(mol, ref_pos)
+    bounds = distance_bounds(mol, ref_pos, stereo=stereo)
     pos, ok, err = embed_conformers_batch([bounds], n, seed=seed, device=device)[0]
     nxt = n
     for _ in range(rounds):

@@ -119,6 +119,7 @@ class Mol:
         self._nbr = None
         self._rings = None
         self.perceived = False
+        self.double_bond_stereo = []      # (a, b, c, d, "cis" | "trans"): a and d flagged on b=c (only a SMILES carries these)
 
     # ---- rdkit-shaped accessors
     def GetAtoms(self): return self.atoms
@@ -302,6 +303,17 @@ def _symmetry_classes(mol: Mol) -> np.ndarray:
         n_cls = k
     _, cls = np.unique(np.asarray(inv, dtype=object).astype(str), return_inverse=True)
     return cls
+
+
+def is_stereocentre(mol: Mol, i, cls) -> bool:
+    """The test a tetrahedral tag has to pass, on a perceived molecule with `cls = _symmetry_classes(mol)`: a heavy sp3 atom with
+    four substituents of which at most one is a hydrogen that is not an atom, all neighbours in different symmetry classes."""
+    a = mol.atoms[i]
+    nb = [j for j, _ in mol.neighbors(i)]
+    if a.z <= 1 or len(nb) + a.num_hs != 4 or len(nb) < 3 or a.num_hs > 1 or a.hybridization != "SP3":
+        return False
+    classes = [cls[j] for j in nb]
+    return len(set(classes)) == len(classes)
 
 
 # ---- perception (restated from rdkit; see the module docstring) -----------------------------------------------------------------------
@@ -519,12 +531,9 @@ def perceive(mol: Mol) -> Mol:
         cls = _symmetry_classes(mol)
         for i, a in enumerate(mol.atoms):
             a.chiral_tag = "CHI_UNSPECIFIED"
+            if not is_stereocentre(mol, i, cls):
+                continue
             nb = [j for j, _ in mol.neighbors(i)]
-            if a.z <= 1 or len(nb) + a.num_hs != 4 or len(nb) < 3 or a.num_hs > 1 or a.hybridization != "SP3":
-                continue
-            classes = [cls[j] for j in nb]
-            if len(set(classes)) != len(classes):
-                continue
             v = [mol.pos[j] - mol.pos[i] for j in nb[:3]]
             vol = float(np.dot(v[0], np.cross(v[1], v[2])))
             if vol < -0.1:
@@ -565,4 +574,6 @@ def remove_hs(mol: Mol) -> Mol:
     bonds = [Bond(remap[b.a], remap[b.b], b.type) for b in mol.bonds if b.a in remap and b.b in remap]
     out = Mol(atoms, bonds, mol.pos[keep] if len(mol.pos) == len(mol.atoms) else mol.pos, name=mol.name)
     out.perceived = mol.perceived
+    out.double_bond_stereo = [tuple(remap[x] for x in rec[:4]) + (rec[4],) for rec in getattr(mol, "double_bond_stereo", [])
+                              if all(x in remap for x in rec[:4])]
     return out

@@ -461,12 +461,13 @@ def generate_conformer(mol, seed=0, device=None):
     """Reference process_mols.py:591-607 with the GPU distance-geometry embedding (datasets/conformer_embedding.py) in place of rdkit's
     ETKDG: up to 3 attempts with fresh conformer ids under `seed`; the first that passes the acceptance test becomes the coordinates of
     `mol` and False is returned.  If none passes, the least-violating one is taken and True ("fell back") is returned.  The molecule's
-    own pose (if it has one that is not flat) fixes the handedness.  The three attempts share one launch."""
+    own pose (if it has one that is not flat) fixes the handedness; a molecule without a conformer (datasets/smiles.py) is embedded
+    with the stereo it carries itself (`stereo="tags"`: chiral tags, `double_bond_stereo`).  The three attempts share one launch."""
     from . import conformer_embedding as ce
     if not mol.perceived:
         perceive(mol)
     ref = mol.GetConformer().GetPositions() if mol.GetNumConformers() else None
-    pos, ok, err = ce.embed_conformers(mol, 3, seed=seed, ref_pos=ref, device=device)
+    pos, ok, err = ce.embed_conformers(mol, 3, seed=seed, ref_pos=ref, device=device, stereo="pose" if ref is not None else "tags")
     good = np.nonzero(ok)[0]
     pick = int(good[0]) if len(good) else int(np.argmin(err))
     mol.pos = pos[pick].copy()

@@ -1,17 +1,35 @@
-"""Dock one ligand into one protein and write the ranked poses: the flow of the reference's dock.py for one complex given as files.
+"""Dock ligands into proteins and write the ranked poses: the flow of the reference's dock.py.
 
-  python tools/dock.py --protein P.pdb[.gz] --ligand L.sdf|.mol2 --out DIR [--samples 10] [--steps 20] [--lm-embeddings E.npy]
-                       [--score-model-dir D --ckpt F] [--confidence-model-dir D --confidence-ckpt F] [--save-visualisation] [--seed 0]
+  python tools/dock.py --out DIR  (--protein P.pdb[.gz] --ligand L.sdf|.mol2
+                                   | --protein P.pdb[.gz] --ligand-description SMILES|L.sdf|L.mol2
+                                   | --protein-ligand-csv FILE)
+                       [--samples 10] [--steps 20] [--lm-embeddings E.npy] [--score-model-dir D --ckpt F]
+                       [--confidence-model-dir D --confidence-ckpt F] [--save-visualisation] [--seed 0]
 
-get_complex -> N shallow copies -> randomize_position -> sampling() with the confidence model -> DIR/rank1.sdf,
-DIR/rank{k}_confidence{c:.2f}.sdf and, with --save-visualisation, DIR/rank{k}_reverseprocess.pdb (the input ligand, the input pose,
-the randomised pose and the pose after every reverse-diffusion step as MODEL frames).
+Three ways to name the input:
+  --ligand FILE               the conformer is SEEDED FROM THE FILE's coordinates (get_complex): bond lengths and angles of the given
+                              pose survive into every docked pose, which flatters a redocking number.  Kept for given poses.
+  --ligand-description TEXT   the reference's front door: a SMILES (datasets/smiles.py) or a path.  The ligand gets a FRESH conformer
+                              from the GPU distance-geometry embedding, also when it came from a file (inference_utils.InferenceDataset).
+  --protein-ligand-csv FILE   columns complex_name, protein_path, ligand_description, protein_sequence (the reference's CSV; an empty
+                              cell is None, a missing name becomes complex_{i}); every row as with --ligand-description.  All rows are
+                              built by one InferenceDataset (one embedding launch); rows that fail are skipped with the reference's
+                              message; the poses of up to eight complexes go through ONE sampling() call; outputs in DIR/<complex_name>/.
+
+per complex: N shallow copies -> randomize_position -> sampling() with the confidence model -> rank1.sdf,
+rank{k}_confidence{c:.2f}.sdf and, with --save-visualisation, rank{k}_reverseprocess.pdb (the input ligand, the input pose, the
+randomised pose and the pose after every reverse-diffusion step as MODEL frames).
 
 A model directory holds model_parameters.yml and the checkpoint.  Without one the model of the shipped architecture is built with
 random weights from --seed: the poses are then meaningless, which is good for a smoke run only.  --lm-embeddings: an .npy of shape
-[residues, 1280] (the ESM2 embeddings of the receptor's residues in file order); without it a zero block is used.  A SMILES ligand,
-computing ESM embeddings and .pdb / .pdbqt ligands are out of scope."""
+[residues, 1280] (the ESM2 embeddings of the receptor's residues in file order; with a CSV it is used for every row); without it a
+zero block is used.
+
+Deviations from rdkit on the SMILES route: no hydrogens are added before embedding; no ETKDG torsion preferences, so an unflagged
+amide may come out cis; no canonicalisation and no SMILES writer; stereo classes beyond @ / @@ and / \\ are refused.  Still out of
+scope: computing ESM embeddings, folding a protein_sequence (a row without a protein_path fails), .pdb / .pdbqt ligands."""
 import argparse
+import csv
 import gzip
 import os
 import sys
@@ -24,6 +42,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+CSV_COLUMNS = ("complex_name", "protein_path", "ligand_description", "protein_sequence")
+CO_SCHEDULED = 8           # complexes per sampling() call: what its co-scheduling advances in one launch
 
 
 def _load_model(model_dir, ckpt, device, seed, confidence_mode):
@@ -39,10 +60,107 @@ def _load_model(model_dir, ckpt, device, seed, confidence_mode):
     return model.to(device).eval(), args
 
 
+def read_protein_ligand_csv(path):
+    """The reference's --protein_ligand_csv (dock.py:53-65, `set_nones`) with the csv module: -> four lists (complex names, protein
+    paths, ligand descriptions, protein sequences), one entry per row; an empty or missing cell is None, a missing name complex_{i}."""
+    with open(path, newline="") as f:
+        rows = list(csv.DictReader(f))
+    cell = lambda row, k: (row.get(k) or "").strip() or None
+    cols = [[cell(row, k) for row in rows] for k in CSV_COLUMNS]
+    cols[0] = [name if name is not None else f"complex_{i}" for i, name in enumerate(cols[0])]
+    return cols
+
+
+def _gunzip(path, tmp, k):
+    if path is None or not path.endswith(".gz"):
+        return path
+    out = os.path.join(tmp, f"{k}_" + os.path.basename(path)[:-3])
+    with gzip.open(path, "rb") as src, open(out, "wb") as dst:
+        dst.write(src.read())
+    return out
+
+
+def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, dev, model, margs, cmodel, cargs):
+    """--ligand-description / --protein-ligand-csv: -> [(name, order, data_list, confidence)] of the complexes that were docked."""
+    from confidence_bootstrapping_amd.datasets import process_mols as pm
+    from confidence_bootstrapping_amd.inference_utils import InferenceDataset
+    from confidence_bootstrapping_amd.sampling import sampling, randomize_position
+    from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
+    from confidence_bootstrapping_amd.visualise import PDBFile
+    from confidence_bootstrapping_amd.docking import write_ranked_poses
+    remove_hs = bool(getattr(margs, "remove_hs", True))
+    with tempfile.TemporaryDirectory() as tmp:
+        proteins = [_gunzip(p, tmp, k) for k, p in enumerate(proteins)]
+        lm = None
+        if "precomputed" in (getattr(model, "lm_embedding_type", None), getattr(cmodel, "lm_embedding_type", None)):
+            if a.lm_embeddings is not None:
+                lm = [np.load(a.lm_embeddings).astype(np.float32)] * len(names)
+            else:
+                print("WARNING: no --lm-embeddings given: the language-model block of the receptor features is ZERO", file=sys.stderr)
+                lm = [None if p is None else np.zeros((len(pm.parse_pdb(p).seq), 1280), dtype=np.float32) for p in proteins]
+        missing = [k for k, p in enumerate(proteins) if p is None]
+        for k in missing:
+            print(f"Skipping {names[k]}: no protein_path (folding a protein_sequence is not covered)")
+        rows = [k for k in range(len(names)) if k not in missing]
+        pick = lambda xs: [xs[k] for k in rows]
+        dataset = InferenceDataset(out_dir=a.out, complex_names=pick(names), protein_files=pick(proteins),
+                                   ligand_descriptions=pick(descriptions), protein_sequences=pick(sequences),
+                                   lm_embeddings=None if lm is None else pick(lm), receptor_radius=getattr(cargs, "receptor_radius", 15.0),
+                                   c_alpha_max_neighbors=getattr(cargs, "c_alpha_max_neighbors", 24), remove_hs=remove_hs, all_atoms=True,
+                                   atom_radius=getattr(cargs, "atom_radius", 5), atom_max_neighbors=getattr(cargs, "atom_max_neighbors", 8),
+                                   device=dev, seed=a.seed)
+        complexes = []
+        for k, idx in enumerate(rows):
+            cplx = dataset[k]
+            if not cplx.success:
+                print(f"HAPPENING | The test dataset did not contain {names[idx]} for {descriptions[idx]} and {proteins[idx]}. "
+                      "We are skipping this complex.")
+                continue
+            complexes.append((idx, cplx))
+    torch.manual_seed(a.seed)
+    np.random.seed(a.seed)
+    sched = get_t_schedule("expbeta", a.steps)
+    chunk = max(d for d in range(1, max(min(a.batch_size, a.samples), 1) + 1) if a.samples % d == 0)      # a chunk never spans two complexes
+    results = []
+    for lo in range(0, len(complexes), CO_SCHEDULED):
+        group = complexes[lo:lo + CO_SCHEDULED]
+        data_list, visualization_list = [], [] if a.save_visualisation else None
+        for _, cplx in group:
+            poses = [cplx.shallow_copy() for _ in range(a.samples)]
+            randomize_position(poses, margs.no_torsion, False, margs.tr_sigma_max)
+            if a.save_visualisation:
+                for graph in poses:
+                    pdb = PDBFile(cplx.mol)
+                    pdb.add(cplx.mol, 0, 0)
+                    pdb.add((cplx["ligand"].pos + cplx.original_center).detach().cpu(), 1, 0)
+                    pdb.add((graph["ligand"].pos + graph.original_center).detach().cpu(), part=1, order=1)
+                    visualization_list.append(pdb)
+            data_list += poses
+        out = sampling(data_list=data_list, model=model, inference_steps=a.steps, tr_schedule=sched, rot_schedule=sched, tor_schedule=sched,
+                       device=dev, t_to_sigma=partial(t_to_sigma, args=margs), model_args=margs, visualization_list=visualization_list,
+                       confidence_model=cmodel, filtering_data_list=[cplx.shallow_copy() for _, cplx in group for _ in range(a.samples)],
+                       filtering_model_args=cargs, batch_size=chunk, no_final_step_noise=a.no_final_step_noise,
+                       return_full_trajectory=a.save_visualisation)
+        data_list, confidence = out[0], out[1]
+        for g, (idx, cplx) in enumerate(group):
+            sl = slice(g * a.samples, (g + 1) * a.samples)
+            order = write_ranked_poses(out_dirs[idx], cplx.mol, data_list[sl], confidence[sl],
+                                       None if visualization_list is None else visualization_list[sl], remove_hs=remove_hs)
+            conf = confidence[sl].detach().cpu().numpy().reshape(a.samples, -1)[:, 0]
+            print(f"{names[idx]}: {a.samples} poses x {a.steps} steps -> {out_dirs[idx]}")
+            for rank, i in enumerate(order[:5]):
+                print(f"  rank {rank + 1}: pose {i:2d}  confidence {conf[i]:+.4f}")
+            results.append((names[idx], order, data_list[sl], confidence[sl]))
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--protein", required=True, help="receptor .pdb or .pdb.gz")
-    ap.add_argument("--ligand", required=True, help="ligand .sdf or .mol2 (its coordinates seed the conformer)")
+    ap.add_argument("--protein", default=None, help="receptor .pdb or .pdb.gz (not needed with --protein-ligand-csv)")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--ligand", default=None, help="ligand .sdf or .mol2 (its coordinates seed the conformer)")
+    src.add_argument("--ligand-description", default=None, help="a SMILES, or a ligand .sdf / .mol2: a fresh conformer is embedded")
+    src.add_argument("--protein-ligand-csv", default=None, help="CSV with the columns " + ", ".join(CSV_COLUMNS))
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--samples", type=int, default=10)
     ap.add_argument("--steps", type=int, default=20)
@@ -56,8 +174,10 @@ def main(argv=None):
     ap.add_argument("--no-final-step-noise", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
-    if not a.ligand.endswith((".sdf", ".mol2")):
+    if a.ligand is not None and not a.ligand.endswith((".sdf", ".mol2")):
         ap.error("the ligand must be an .sdf or .mol2 file")
+    if a.protein_ligand_csv is None and a.protein is None:
+        ap.error("--protein is required with --ligand and --ligand-description")
     from confidence_bootstrapping_amd.datasets import process_mols as pm
     from confidence_bootstrapping_amd.sampling import sampling, randomize_position
     from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
@@ -68,6 +188,15 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     model, margs = _load_model(a.score_model_dir, a.ckpt, dev, a.seed, False)
     cmodel, cargs = _load_model(a.confidence_model_dir, a.confidence_ckpt, dev, a.seed + 5, True)
+    if a.protein_ligand_csv is not None:
+        names, proteins, descriptions, sequences = read_protein_ligand_csv(a.protein_ligand_csv)
+        return _dock_descriptions(a, names, proteins, descriptions, sequences, [os.path.join(a.out, n) for n in names], dev, model, margs,
+                                  cmodel, cargs)
+    if a.ligand_description is not None:
+        done = _dock_descriptions(a, ["complex_0"], [a.protein], [a.ligand_description], [None], [a.out], dev, model, margs, cmodel, cargs)
+        if not done:
+            raise ValueError(f"could not dock {a.ligand_description!r}: see the message above")
+        return done[0][1:]
     with tempfile.TemporaryDirectory() as tmp:
         protein = a.protein
         if protein.endswith(".gz"):
