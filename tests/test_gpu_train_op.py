@@ -1,5 +1,6 @@
 """Training op (csrc/tp_train.hip via cbd_tp_forward / cbd_tp_backward) against autograd through the oracle's restatement of the
-reference FasterTensorProduct + last FCBlock Linear (oracle/score_ref.py::faster_tensor_product, models/tensor_layers.py:66-117)."""
+reference FasterTensorProduct + last FCBlock Linear (oracle/score_ref.py::faster_tensor_product, models/tensor_layers.py:66-117).
+The production path (StreamHub + TensorProductHubFn) against fp64 within a-priori bounds: tests/test_gpu_tp_train.py."""
 import numpy as np
 import pytest
 import torch
