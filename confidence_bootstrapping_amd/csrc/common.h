@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace cbd {
 
 // Weight streams are read through address-space-1 pointers (`GPtr`, reduce_runs.h) with a WAVE-UNIFORM base: global_load with an SGPR
@@ -73,6 +75,18 @@ __host__ __device__ constexpr ConvShape conv_shape(int IN, int OUT, bool merged 
   s.in_dim = NS + 3 * s.n1o + 3 * s.n1e + s.n0o;
   s.out_dim = NS + 3 * NV + (OUT >= 2 ? 3 * NV : 0) + (OUT >= 3 ? NV : 0);
   return s;
+}
+
+// The four (input level, output level) pairs of the interaction layers as compile-time constants: calls
+// f(integral_constant<int, IN>{}, integral_constant<int, OUT>{}) of the matching pair; any other pair is hipErrorInvalidValue.
+template <class F>
+inline hipError_t dispatch_levels(int in_level, int out_level, F&& f) {
+  using std::integral_constant;
+  if (in_level == 0 && out_level == 1) return f(integral_constant<int, 0>{}, integral_constant<int, 1>{});
+  if (in_level == 1 && out_level == 2) return f(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+  if (in_level == 2 && out_level == 3) return f(integral_constant<int, 2>{}, integral_constant<int, 3>{});
+  if (in_level == 3 && out_level == 3) return f(integral_constant<int, 3>{}, integral_constant<int, 3>{});
+  return hipErrorInvalidValue;
 }
 
 struct ConvGroup {

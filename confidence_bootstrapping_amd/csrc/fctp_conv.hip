@@ -465,11 +465,7 @@ static hipError_t launch_fctp_one(const CArgs& a, int grid, hipStream_t s) {
 
 hipError_t launch_fctp_conv(int in_level, int out_level, const CArgs& a, int grid, hipStream_t s) {
   if (grid <= 0) return hipSuccess;
-  if (in_level == 0 && out_level == 1) return launch_fctp_one<0, 1>(a, grid, s);
-  if (in_level == 1 && out_level == 2) return launch_fctp_one<1, 2>(a, grid, s);
-  if (in_level == 2 && out_level == 3) return launch_fctp_one<2, 3>(a, grid, s);
-  if (in_level == 3 && out_level == 3) return launch_fctp_one<3, 3>(a, grid, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_fctp_one<decltype(in)::value, decltype(out)::value>(a, grid, s); });
 }
 
 hipError_t launch_fctp_finalize(const CFinArgs& fa, const float* node_in, float* node_out, const float* bn_scale,

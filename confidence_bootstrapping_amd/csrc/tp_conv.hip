@@ -6,8 +6,9 @@
 // replacing reference models/tensor_layers.py:195-206 (FCBlock -> FasterTensorProduct.forward:66-117 ->
 // torch_scatter.scatter) without ever materialising the [E, W] per-edge weight tensor in HBM.
 //
-// Mapping onto the matrix cores (described for the exact-fp32 policy OpsF32, v_mfma_f32_32x32x2_f32; OpsBf16 below is the
-// bf16-operand policy of the same kernel):
+// Mapping onto the matrix cores (described for the exact-fp32 policy OpsF32, v_mfma_f32_32x32x2_f32; OpsBf16x3, the three-plane
+// bf16 split of fp32 operands, is the other policy of the same kernel -- both in tp_conv_dev.h; the bf16-operand kernels are
+// tp_conv_bf16.hip / tp_conv_bf16s.hip):
 //   D[row = weight column, col = edge] = sum_k  A[row][k] * B[k][edge]
 //   * B (activations) lives in registers for the whole tile: lane (j = lane&31, hf = lane>>5) holds
 //     act[edge j][k(s, hf)] for the 48 k-steps s.  The accumulator of the first Linear (after bias+ReLU) IS the
@@ -58,19 +59,13 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
 
   // ---- start the weight stream: tile 0 fragments + the bias table of the group
   using Frag = typename Ops::Frag;
-  // NODE_PROJ policies: wave-uniform stream base, tile T fragment sg of this lane = gu[T * TILE_FRAGS + sg * 64 + lane]
+  // wave-uniform stream base, tile T fragment sg of this lane = gu[T * TILE_FRAGS + sg * 64 + lane]
   const GPtr<Frag> gu = (GPtr<Frag>)reinterpret_cast<const Frag*>(G.wstream);
-  const Frag* gp = reinterpret_cast<const Frag*>(G.wstream) + lane;   // per-lane form (policies without NODE_PROJ)
   Frag a[Ops::NFRAG];
-  if constexpr (Ops::NODE_PROJ) {
-    // the live fragments of all three first-Linear tiles (f32_split: tiles 0 and 1 here, tile 2 behind the row gather below -- all 18
-    // of its fragments in flight next to the gathers cost a spill and a wait on it at the very start of the wave)
-    if constexpr (std::is_same<Ops, OpsBf16x3>::value) Ops::template load_first_part<0, 2>(a, gu, lane);
-    else Ops::load_first_u(a, gu, lane);
-  } else {
-#pragma unroll
-    for (int sg = 0; sg < Ops::NFRAG; ++sg) a[sg] = gp[sg * 64];
-  }
+  // the live fragments of all three first-Linear tiles (f32_split: tiles 0 and 1 here, tile 2 behind the row gather below -- all 18
+  // of its fragments in flight next to the gathers cost a spill and a wait on it at the very start of the wave)
+  if constexpr (std::is_same<Ops, OpsBf16x3>::value) Ops::template load_first_part<0, 2>(a, gu, lane);
+  else Ops::load_first(a, gu, lane);
   {  // bias table -> LDS: fixed number of unconditional, clamped loads (a counted loop compiles to a load/wait waterfall)
     const f32x4* gb = reinterpret_cast<const f32x4*>(reinterpret_cast<const Frag*>(G.wstream) + (size_t)(S.ntiles + 1) * Ops::TILE_FRAGS);
     constexpr int NB4 = S.ntiles * 8, NBI = (NB4 + 63) / 64;
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
   const float v[3] = {vv.x, vv.y, vv.z};
   if (hf == 0) srcl[j] = src;
 
-  f32x16 acc1[Ops::NODE_PROJ ? 3 : 1];
+  f32x16 acc1[3];
   typename Ops::Act Bx;  // first-Linear input on the matrix cores: edge_attr(32), lane half hf holds cols 16hf..16hf+15.  The
                          // x_src[:32] / x_dst[:32] parts arrive as per-node projections through the accumulator (G.psrc / G.pdst)
   {
@@ -102,32 +97,21 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
     const f32x4* pa = reinterpret_cast<const f32x4*>(G.attr + (size_t)aidx * 32 + 16 * hf);
 #pragma unroll
     for (int q = 0; q < 4; ++q) Ops::set_in(Bx, 0, q, gl(pa + q));
-    if constexpr (!Ops::NODE_PROJ) {
-      const f32x4* ps = reinterpret_cast<const f32x4*>(G.node_in + (size_t)src_r * NODE_STRIDE + 16 * hf);
-      const f32x4* pd = reinterpret_cast<const f32x4*>(G.node_in + (size_t)dst * NODE_STRIDE + 16 * hf);
+    // accumulator start values of the three first-Linear tiles, gathered HERE with everything else the edge needs (the first Linear
+    // then waits on nothing): b1 + W1s x_src + W1d x_dst for rows 32m + (r&3) + 8(r>>2) + 4hf; the bias rows straight from the
+    // stream's table in global memory (its LDS copy is still being written)
+    const f32x4* const gb = reinterpret_cast<const f32x4*>(reinterpret_cast<const Frag*>(G.wstream) + (size_t)(S.ntiles + 1) * Ops::TILE_FRAGS);
+    const f32x4* const p_s = reinterpret_cast<const f32x4*>(G.psrc + (size_t)src_r * KDIM + 4 * hf);
+    const f32x4* const p_d = reinterpret_cast<const f32x4*>(G.pdst + (size_t)dst * KDIM + 4 * hf);
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        Ops::set_in(Bx, 1, q, ps[q]);
-        Ops::set_in(Bx, 2, q, pd[q]);
+        const f32x4 b = gb[8 * m + 2 * q + hf];
+        const f32x4 u = gl(p_s + 8 * m + 2 * q), w = gl(p_d + 8 * m + 2 * q);
+        acc1[m][4 * q + 0] = b.x + u.x + w.x; acc1[m][4 * q + 1] = b.y + u.y + w.y;
+        acc1[m][4 * q + 2] = b.z + u.z + w.z; acc1[m][4 * q + 3] = b.w + u.w + w.w;
       }
-    }
-    if constexpr (Ops::NODE_PROJ) {
-      // accumulator start values of the three first-Linear tiles, gathered HERE with everything else the edge needs (the first Linear
-      // then waits on nothing): b1 + W1s x_src + W1d x_dst for rows 32m + (r&3) + 8(r>>2) + 4hf; the bias rows straight from the
-      // stream's table in global memory (its LDS copy is still being written)
-      const f32x4* const gb = reinterpret_cast<const f32x4*>(reinterpret_cast<const Frag*>(G.wstream) + (size_t)(S.ntiles + 1) * Ops::TILE_FRAGS);
-      const f32x4* const p_s = reinterpret_cast<const f32x4*>(G.psrc + (size_t)src_r * KDIM + 4 * hf);
-      const f32x4* const p_d = reinterpret_cast<const f32x4*>(G.pdst + (size_t)dst * KDIM + 4 * hf);
-#pragma unroll
-      for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 b = gb[8 * m + 2 * q + hf];
-          const f32x4 u = gl(p_s + 8 * m + 2 * q), w = gl(p_d + 8 * m + 2 * q);
-          acc1[m][4 * q + 0] = b.x + u.x + w.x; acc1[m][4 * q + 1] = b.y + u.y + w.y;
-          acc1[m][4 * q + 2] = b.z + u.z + w.z; acc1[m][4 * q + 3] = b.w + u.w + w.w;
-        }
-    }
     // full destination row -> transposed LDS copy xT[col][j]; lane half hf copies cols 40hf .. 40hf+39
     // (f32_split: its 18-fragment weight tile + three-plane operands leave no room for the row's 40 registers NEXT TO the 48 start
     //  values above -- hipcc spilled 12 registers here; a scheduling fence makes the row gather a round of its own.  One extra memory
@@ -154,8 +138,7 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
 #define CBD_TILE(BOP, NEXT)                                                                         \
   {                                                                                                 \
     const int tn_ = (NEXT);                                                                         \
-    if constexpr (Ops::NODE_PROJ) gemm_tile_u<Ops>(a, gu + (size_t)tn_ * Ops::TILE_FRAGS, lane, bias_l + T * 32, BOP, acc, hf); \
-    else gemm_tile<Ops>(a, gp + (size_t)tn_ * Ops::TILE_FRAGS, bias_l + T * 32, BOP, acc, hf); \
+    gemm_tile<Ops>(a, gu + (size_t)tn_ * Ops::TILE_FRAGS, lane, bias_l + T * 32, BOP, acc, hf);     \
     T = tn_;                                                                                        \
   }
 
@@ -165,24 +148,16 @@ __global__ __launch_bounds__(64, 2) void tp_conv_kernel(ConvArgs args) {
   const int i_lo = G.i0e_lo, i_hi = G.i0e_hi;
   const bool vec_on = G.vec_on != 0;
   const int T_vec = 3 + S.t0e;
-  if constexpr (!Ops::NODE_PROJ) {
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      CBD_TILE(Bx, m < 2 ? T + 1 : (i_lo < i_hi ? 3 + i_lo : T_vec));
-      if constexpr (!Ops::EXACT_F32) { if (m == 2) mfma_operand_guard(); }   // the first-Linear operands die here without a refill
-      Ops::set_hidden(h1, m, acc);
-      if constexpr (STAMPS) { if (m == 0) st_g0 = stamp(); }
-    }
-  } else {
+  {
     // K = 32 edge-attribute product on top of acc1[m]; tile m's registers are refilled with the first second-Linear tile's fragments
     const int tn_ = i_lo < i_hi ? 3 + i_lo : T_vec;
     const GPtr<Frag> next = gu + (size_t)tn_ * Ops::TILE_FRAGS;
-    Ops::template gemm_first_u<0>(a, next, lane, Bx, acc1[0]);
+    Ops::template gemm_first<0>(a, next, lane, Bx, acc1[0]);
     Ops::set_hidden(h1, 0, acc1[0]);
     if constexpr (STAMPS) st_g0 = stamp();
-    Ops::template gemm_first_u<1>(a, next, lane, Bx, acc1[1]);
+    Ops::template gemm_first<1>(a, next, lane, Bx, acc1[1]);
     Ops::set_hidden(h1, 1, acc1[1]);
-    Ops::template gemm_first_u<2>(a, next, lane, Bx, acc1[2]);
+    Ops::template gemm_first<2>(a, next, lane, Bx, acc1[2]);
     if constexpr (!Ops::EXACT_F32) mfma_operand_guard();   // Bx dies here without a refill
     Ops::set_hidden(h1, 2, acc1[2]);
     T = tn_;
@@ -460,7 +435,7 @@ __global__ __launch_bounds__(64) void bond_conv_kernel(BondHead h, Multi mm, int
   const float* P = pos + (size_t)b * Nl * 3;
   const int u = gs.rot_u[rho], v = gs.rot_v[rho];
 
-  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: gemm_u)
+  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: OpsF32::gemm)
   f32x4 a[KSTEPS / 4];
 #pragma unroll
   for (int sg = 0; sg < KSTEPS / 4; ++sg) a[sg] = gp[sg * 64 + lane];
@@ -538,7 +513,7 @@ __global__ __launch_bounds__(64) void bond_conv_kernel(BondHead h, Multi mm, int
   OpsF32::Act h1;
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
-    gemm_tile_u<OpsF32>(a, gp + (size_t)(T + 1) * (TILE_W_FLOATS / 4), lane, bias_l + T * 32, BxA, acc, hf);
+    gemm_tile<OpsF32>(a, gp + (size_t)(T + 1) * (TILE_W_FLOATS / 4), lane, bias_l + T * 32, BxA, acc, hf);
     ++T;
     OpsF32::set_hidden(h1, m, acc);
   }
@@ -547,7 +522,7 @@ __global__ __launch_bounds__(64) void bond_conv_kernel(BondHead h, Multi mm, int
   for (int r = 0; r < 16; ++r) { oA[r] = 0.f; oB[r] = 0.f; }
 #pragma unroll
   for (int q = 0; q < 12; ++q) {
-    gemm_tile_u<OpsF32>(a, gp + (size_t)(T + 1) * (TILE_W_FLOATS / 4), lane, bias_l + T * 32, h1, acc, hf);
+    gemm_tile<OpsF32>(a, gp + (size_t)(T + 1) * (TILE_W_FLOATS / 4), lane, bias_l + T * 32, h1, acc, hf);
     ++T;
     if (q < 6) {
 #pragma unroll
@@ -607,7 +582,8 @@ static hipError_t launch_one(const ConvArgs& a, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The bf16-operand variant (cbd_set_option("bf16", 1), BASELINE.json configs[3]) lives in tp_conv_bf16.hip (64 edges per wave).
+// The same kernel with the three-plane bf16 split of its fp32 operands (OpsBf16x3, cbd_set_option("f32_split", 1)).  The bf16-operand
+// variant (cbd_set_option("bf16", 1), BASELINE.json configs[3]) is a kernel of its own in tp_conv_bf16.hip (64 edges per wave).
 template <int IN, int OUT>
 static hipError_t launch_one_x3(const ConvArgs& a, int grid, hipStream_t s) {
   constexpr int lds_bytes = conv_lds_floats(conv_shape(IN, OUT, true).ntiles) * 4;
@@ -617,20 +593,12 @@ static hipError_t launch_one_x3(const ConvArgs& a, int grid, hipStream_t s) {
 
 hipError_t launch_tp_conv_x3(int in_level, int out_level, const ConvArgs& a, int grid, hipStream_t s) {
   if (grid <= 0) return hipSuccess;
-  if (in_level == 0 && out_level == 1) return launch_one_x3<0, 1>(a, grid, s);
-  if (in_level == 1 && out_level == 2) return launch_one_x3<1, 2>(a, grid, s);
-  if (in_level == 2 && out_level == 3) return launch_one_x3<2, 3>(a, grid, s);
-  if (in_level == 3 && out_level == 3) return launch_one_x3<3, 3>(a, grid, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_one_x3<decltype(in)::value, decltype(out)::value>(a, grid, s); });
 }
 
 hipError_t launch_tp_conv(int in_level, int out_level, const ConvArgs& a, int grid, hipStream_t s) {
   if (grid <= 0) return hipSuccess;
-  if (in_level == 0 && out_level == 1) return launch_one<0, 1>(a, grid, s);
-  if (in_level == 1 && out_level == 2) return launch_one<1, 2>(a, grid, s);
-  if (in_level == 2 && out_level == 3) return launch_one<2, 3>(a, grid, s);
-  if (in_level == 3 && out_level == 3) return launch_one<3, 3>(a, grid, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_one<decltype(in)::value, decltype(out)::value>(a, grid, s); });
 }
 
 hipError_t launch_conv_finalize(const FinArgs& fa, const float* node_in, float* node_out, const float* bn_scale,

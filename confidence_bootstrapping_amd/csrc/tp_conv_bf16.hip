@@ -472,11 +472,7 @@ static hipError_t launch_one64(const ConvArgs& a, int grid, hipStream_t s) {
 // grid: number of 64-edge waves (sum over groups of ceil(cap / 64))
 hipError_t launch_tp_conv_bf16(int in_level, int out_level, const ConvArgs& a, int grid, hipStream_t s) {
   if (grid <= 0) return hipSuccess;
-  if (in_level == 0 && out_level == 1) return launch_one64<0, 1>(a, grid, s);
-  if (in_level == 1 && out_level == 2) return launch_one64<1, 2>(a, grid, s);
-  if (in_level == 2 && out_level == 3) return launch_one64<2, 3>(a, grid, s);
-  if (in_level == 3 && out_level == 3) return launch_one64<3, 3>(a, grid, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_one64<decltype(in)::value, decltype(out)::value>(a, grid, s); });
 }
 
 }  // namespace cbd

@@ -30,6 +30,26 @@ __device__ __forceinline__ void v2_set_hidden(Act6& h, int m, const f32x16& acc)
   for (int r = 0; r < 16; ++r) h.v[2 * m + (r >> 3)][r & 7] = (__bf16)relu1(acc[r]);
 }
 
+// The next tile's 32 bias floats, one dword per lane (`raw_next`: lane l holds float l & 31), spread into the accumulator layout `cb`
+// through the LDS crossbar (ds_bpermute_b32, no LDS memory): register r of lane half hf is weight row (r & 3) + 8 (r >> 2) + 4 hf.
+// inline asm: the builtin takes no offset, and hipcc then keeps 16 address registers (spills); with the instruction's offset
+// field one address register (`lane4hf`: byte address of lane 4 hf) serves all 16.  The results are NOT tracked by the compiler's
+// waitcnt insertion: bias_ready() (s_waitcnt lgkmcnt(0)) closes the tile's epilogue before cb is read again.
+__device__ __forceinline__ void v2_spread_bias(f32x16& cb, int lane4hf, float raw_next) {
+  float t[16];
+#define CBD_BP4(R, O0, O1, O2, O3)                                                                                      \
+  asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
+               "\n\tds_bpermute_b32 %2, %4, %5 offset:" #O2 "\n\tds_bpermute_b32 %3, %4, %5 offset:" #O3            \
+               : "=&v"(t[R]), "=&v"(t[R + 1]), "=&v"(t[R + 2]), "=&v"(t[R + 3]) : "v"(lane4hf), "v"(raw_next))
+  CBD_BP4(0, 0, 4, 8, 12);
+  CBD_BP4(4, 32, 36, 40, 44);
+  CBD_BP4(8, 64, 68, 72, 76);
+  CBD_BP4(12, 96, 100, 104, 108);
+#undef CBD_BP4
+#pragma unroll
+  for (int r = 0; r < 16; ++r) cb[r] = t[r];
+}
+
 // acc_s = bias + A_tile * B_s (s = 0, 1).  The bias (fp32, one value per weight row) sits in 16 registers in the accumulator layout
 // and is the C operand of the first MFMA pair (D != C): no bias k-step, no accumulator initialisation.
 // The A fragments and the bias registers are refilled in place with the NEXT tile's data.  Two rules keep the in-flight MFMA operand
@@ -69,24 +89,9 @@ __device__ __forceinline__ void v2_gemm(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFrag
     if (q == V2_NFRAG - 1) a[q] = pb[lane + (q - 4) * 64];
     __builtin_amdgcn_sched_barrier(0);
   }
-  // ... spread into the accumulator layout through the LDS crossbar (ds_bpermute_b32, no LDS memory): register r of lane half hf is
-  // weight row (r & 3) + 8 (r >> 2) + 4 hf.  Issued behind the last pair: pair 0, which read cb as its C operand, has executed long ago,
-  // and the tile's CG epilogue covers the crossbar latency.
-  // inline asm: the builtin takes no offset, and hipcc then keeps 16 address registers (spills); with the instruction's offset
-  // field one address register (byte address of lane 4 hf) serves all 16.  The results are NOT tracked by the compiler's waitcnt
-  // insertion: bias_ready() (s_waitcnt lgkmcnt(0)) closes the tile's epilogue before cb is read again.
-  float t[16];
-#define CBD_BP4(R, O0, O1, O2, O3)                                                                                      \
-  asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
-               "\n\tds_bpermute_b32 %2, %4, %5 offset:" #O2 "\n\tds_bpermute_b32 %3, %4, %5 offset:" #O3            \
-               : "=&v"(t[R]), "=&v"(t[R + 1]), "=&v"(t[R + 2]), "=&v"(t[R + 3]) : "v"(lane4hf), "v"(raw_next))
-  CBD_BP4(0, 0, 4, 8, 12);
-  CBD_BP4(4, 32, 36, 40, 44);
-  CBD_BP4(8, 64, 68, 72, 76);
-  CBD_BP4(12, 96, 100, 104, 108);
-#undef CBD_BP4
-#pragma unroll
-  for (int r = 0; r < 16; ++r) cb[r] = t[r];
+  // ... spread into the accumulator layout (v2_spread_bias).  Issued behind the last pair: pair 0, which read cb as its C operand, has
+  // executed long ago, and the tile's CG epilogue covers the crossbar latency.
+  v2_spread_bias(cb, lane4hf, raw_next);
   raw_next = raw_new;
   __builtin_amdgcn_sched_barrier(0);
 }
@@ -127,20 +132,7 @@ __device__ __forceinline__ void v2_gemm_p(bf16x8 (&a)[V2_NFRAG], f32x16& cb, GFr
     if (q > 0) a[q - 1] = q - 1 < 4 ? pa[lane + (q - 1) * 64] : pb[lane + (q - 5) * 64];
     if (q == V2_NFRAG - 1) a[q] = pb[lane + (q - 4) * 64];
     __builtin_amdgcn_sched_barrier(0);
-    if (q == 3 && BIAS) {
-      float t[16];
-#define CBD_BP4(R, O0, O1, O2, O3)                                                                                      \
-      asm volatile("ds_bpermute_b32 %0, %4, %5 offset:" #O0 "\n\tds_bpermute_b32 %1, %4, %5 offset:" #O1                \
-                   "\n\tds_bpermute_b32 %2, %4, %5 offset:" #O2 "\n\tds_bpermute_b32 %3, %4, %5 offset:" #O3            \
-                   : "=&v"(t[R]), "=&v"(t[R + 1]), "=&v"(t[R + 2]), "=&v"(t[R + 3]) : "v"(lane4hf), "v"(raw_next))
-      CBD_BP4(0, 0, 4, 8, 12);
-      CBD_BP4(4, 32, 36, 40, 44);
-      CBD_BP4(8, 64, 68, 72, 76);
-      CBD_BP4(12, 96, 100, 104, 108);
-#undef CBD_BP4
-#pragma unroll
-      for (int r = 0; r < 16; ++r) cb[r] = t[r];
-    }
+    if (q == 3 && BIAS) v2_spread_bias(cb, lane4hf, raw_next);
     epi(q);
     if (q < V2_NFRAG - 1) asm volatile("" ::"v"(a[q]));   // fragment q stays allocated until its re-load behind pair q + 1
     __builtin_amdgcn_sched_barrier(0);

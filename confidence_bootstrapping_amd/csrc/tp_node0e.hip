@@ -38,7 +38,7 @@ __global__ __launch_bounds__(64) void node0e_build_kernel(N0eArgs args) {
   const N0eGroup& G = args.g[g];
   const GPtr<f32x4> gu = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(G.wstream);
   f32x4 a[OpsF32::NFRAG];
-  OpsF32::load_first_u(a, gu, lane);                  // the three first-Linear tiles stay in registers for all nodes of the wave
+  OpsF32::load_first(a, gu, lane);                    // the three first-Linear tiles stay in registers for all nodes of the wave
   const f32x4* const gb = reinterpret_cast<const f32x4*>(G.wstream + (size_t)(conv_shape(3, 3, true).ntiles + 1) * TILE_W_FLOATS);
   for (int i = lane; i < WAVE_EDGES * TS; i += 64) tT[i] = 0.f;
 
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64) void node0e_gemm_kernel(N0eArgs args) {
   // the stream's next tile after the last 0e one is the first vector tile: every prefetch is in bounds
   for (int jj = 0; jj < N0E_MIDS; ++jj) {
     load_b(Bn, jj + 1 < N0E_MIDS ? jj + 1 : jj);
-    OpsF32::gemm_u(a, gu + (size_t)(T0 + jj + 1) * OpsF32::TILE_FRAGS, lane, B, acc);
+    OpsF32::gemm(a, gu + (size_t)(T0 + jj + 1) * OpsF32::TILE_FRAGS, lane, B, acc);
     B = Bn;
   }
   // bias term sum_j b2_j[w] S[j], fixed order

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(64, 2) void tp_train_fwd_kernel(TrainTpArgs A) {
   const int e = e0 + j;
   const int ec = e < e_end ? e : e_end - 1;
   const float* const wstream = A.wstream[grp];
-  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: gemm_u)
+  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: OpsF32::gemm)
   f32x4 a[OpsF32::NFRAG];
   OpsF32::Act h1;
   train_prologue<IN, OUT>(A, wstream, bias_l, xT, lane, ec, gp, a, h1);
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(64, 2) void tp_train_fwd_kernel(TrainTpArgs A) {
   f32x16 acc;
 #define CBD_TT()                                                                                              \
   {                                                                                                           \
-    gemm_tile_u<OpsF32>(a, gp + (size_t)(T + 1) * OpsF32::TILE_FRAGS, lane, bias_l + T * 32, h1, acc, hf);            \
+    gemm_tile<OpsF32>(a, gp + (size_t)(T + 1) * OpsF32::TILE_FRAGS, lane, bias_l + T * 32, h1, acc, hf);              \
     ++T;                                                                                                      \
   }
   const float* xc = xT + j;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64, 2) void tp_train_bwd_kernel(TrainTpArgs A) {
   const bool valid = e < e_end;
   const int ec = valid ? e : e_end - 1;
   const float* const wstream = A.wstream[grp];
-  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: gemm_u)
+  const GPtr<f32x4> gp = (GPtr<f32x4>)reinterpret_cast<const f32x4*>(wstream);   // wave-uniform stream base (tp_conv_dev.h: OpsF32::gemm)
   f32x4 a[OpsF32::NFRAG];
   OpsF32::Act h1;
   train_prologue<IN, OUT>(A, wstream, nullptr, xT, lane, ec, gp, a, h1);
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(64, 2) void tp_train_bwd_kernel(TrainTpArgs A) {
       pin_s(pb);                                                                                              \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) bq[q] = pb[hf + 2 * q];                                   \
     }                                                                                                         \
-    OpsF32::gemm_u(a, gp + (size_t)(T + 1) * OpsF32::TILE_FRAGS, lane, h1, acc);                              \
+    OpsF32::gemm(a, gp + (size_t)(T + 1) * OpsF32::TILE_FRAGS, lane, h1, acc);                                \
     ++T;                                                                                                      \
   }
   const float* xc = xT + j;
@@ -435,11 +435,7 @@ static hipError_t launch_train(bool bwd, const TrainTpArgs& a, hipStream_t s) {
 }
 
 static hipError_t launch_train_any(int in_level, int out_level, bool bwd, const TrainTpArgs& a, hipStream_t s) {
-  if (in_level == 0 && out_level == 1) return launch_train<0, 1>(bwd, a, s);
-  if (in_level == 1 && out_level == 2) return launch_train<1, 2>(bwd, a, s);
-  if (in_level == 2 && out_level == 3) return launch_train<2, 3>(bwd, a, s);
-  if (in_level == 3 && out_level == 3) return launch_train<3, 3>(bwd, a, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_train<decltype(in)::value, decltype(out)::value>(bwd, a, s); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -585,11 +581,7 @@ static hipError_t launch_train_gh(const TrainTpArgs& a, hipStream_t s) {
 }
 
 static hipError_t launch_train_gh_any(int in_level, int out_level, const TrainTpArgs& a, hipStream_t s) {
-  if (in_level == 0 && out_level == 1) return launch_train_gh<0, 1>(a, s);
-  if (in_level == 1 && out_level == 2) return launch_train_gh<1, 2>(a, s);
-  if (in_level == 2 && out_level == 3) return launch_train_gh<2, 3>(a, s);
-  if (in_level == 3 && out_level == 3) return launch_train_gh<3, 3>(a, s);
-  return hipErrorInvalidValue;
+  return dispatch_levels(in_level, out_level, [&](auto in, auto out) { return launch_train_gh<decltype(in)::value, decltype(out)::value>(a, s); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -985,11 +977,8 @@ int cbd_tp_backward_gh(int32_t in_level, int32_t out_level, int32_t n_groups, co
 
 static int launch_dw_any(int32_t in_level, int32_t out_level, const cbd::TrainDwArgs& a, int total_chunks, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipError_t r = hipErrorInvalidValue;
-  if (in_level == 0 && out_level == 1) r = cbd::launch_train_dw<0, 1>(a, total_chunks, st);
-  else if (in_level == 1 && out_level == 2) r = cbd::launch_train_dw<1, 2>(a, total_chunks, st);
-  else if (in_level == 2 && out_level == 3) r = cbd::launch_train_dw<2, 3>(a, total_chunks, st);
-  else if (in_level == 3 && out_level == 3) r = cbd::launch_train_dw<3, 3>(a, total_chunks, st);
+  const hipError_t r = cbd::dispatch_levels(
+      in_level, out_level, [&](auto in, auto out) { return cbd::launch_train_dw<decltype(in)::value, decltype(out)::value>(a, total_chunks, st); });
   if (r != hipSuccess) return fail(r == hipErrorInvalidValue ? CBD_ERR_ARG : CBD_ERR_HIP, "cbd_tp_backward_dw: %s", hipGetErrorString(r));
   return 0;
 }
