@@ -18,6 +18,7 @@ import torch
 from .engine import DockEngine, make_steps
 from .hetero import Batch
 from .sampling import randomize_position, randomize_position_batch
+from .wave_pipeline import Group, LoaderBatch, WavePipeline, score_wave, switch_on_async_setup
 
 
 class ComplexSetRunner:
@@ -32,22 +33,13 @@ class ComplexSetRunner:
         self.sched = get_t_schedule("expbeta", self.S)
         self.steps = make_steps(self.sched, score_args, score_model.timestep_emb_func)
         # two alternating sets of `group` engines (the partners share the first engine's weights): the complexes of the NEXT group are
-        # set up on the idle set while the current group runs (cbd_set_complex with "async_setup", uploads on a side stream)
+        # set up on the idle set while the current group runs (wave_pipeline: cbd_set_complex with "async_setup", uploads on a side stream)
         self.engines = [DockEngine.from_model(score_model, self.dev, max_batch=self.samples)]
-        for _ in range(2 * self.group - 1):
-            p = DockEngine(self.dev, max_batch=self.samples, lm_embedding_dim=self.engines[0].cfg.lm_embedding_dim,
-                           no_torsion=bool(self.engines[0].cfg.no_torsion))
-            p.share_weights_from(self.engines[0])
-            self.engines.append(p)
-        for e in self.engines:
-            e.set_option("async_setup", 1)
+        self.engines += [self.engines[0].partner() for _ in range(2 * self.group - 1)]
+        switch_on_async_setup(self.engines, {})
         self.sets = [self.engines[:self.group], self.engines[self.group:]]
-        self.side = torch.cuda.Stream(self.dev)
-        # event on the current stream recorded just before a group is launched: the side-stream fills of the NEXT group follow everything
-        # queued up to it (their buffers come from the current stream's allocator pool and may have been freed by the host while work
-        # queued there still reads them -- ADVICE round 5), but not the running group itself
-        self._fill_after = None
-        self._staged = None          # (indices, set, staged inputs) of the group prepared ahead
+        self.pipe = WavePipeline(self.dev, self.sets)
+        self._ahead = None           # the group staged ahead: (its complex indices, engine set, wave_pipeline.Staged per complex)
         self._turn = 0
         self.ceng = conf_model.engine(max_batch=self.samples) if conf_model is not None else None
         # one confidence engine per complex of a group: up to four complexes are scored in ONE set of fused-conv launches
@@ -82,76 +74,46 @@ class ComplexSetRunner:
         self.prepared[i] = (cplx, pos0, noise)
         return self.prepared[i]
 
-    def _stage(self, items, which, ahead=False):
-        """set-up of every complex of a group on engine set `which` + its pose / noise uploads (device buffers from the current stream's
-        pool, filled on the side stream: an allocation ON the side stream would wait for the running group)"""
-        def up(t):
-            t = t.to(torch.float32).contiguous()
-            d = torch.empty(t.shape, dtype=torch.float32, device=self.dev)
-            with torch.cuda.stream(self.side):
-                d.copy_(t, non_blocking=True)
-            return d
-        if ahead and self._fill_after is not None:
-            self.side.wait_event(self._fill_after)
-        else:       # nothing of this runner is on the GPU: simply behind whatever the caller has queued
-            self.side.wait_stream(torch.cuda.current_stream(self.dev))
-        staged = []
-        for e, (i, c) in zip(self.sets[which], items):
+    def _groups(self, items):
+        groups = []
+        for i, c in items:
             cplx, pos0, noise = self.prepared[i] if i in self.prepared else self.prepare(i, c)
-            e.set_complex(cplx)
-            staged.append((up(pos0), [up(z) for z in noise]))
-        return staged
+            groups.append(Group(cplx, None, [LoaderBatch(i, pos0, noise, cplx)]))
+        return groups
 
     def sample_group(self, items: Sequence, next_items: Sequence = None) -> List[dict]:
         """`items` = [(index, complex), ...] (<= group): set-up of every complex (graph upload, receptor embedding, all-atom tables),
         ONE co-scheduled sampling call, confidence ranking.  One picklable dict per complex.  `next_items`: the group that will be
         asked for next -- its set-up runs on the other engine set while this group's step loop is on the GPU."""
         ta = time.perf_counter()
-        key = tuple(i for i, _ in items)
-        if self._staged is not None and self._staged[0] == key:
-            _, which, staged = self._staged
-        else:
-            which, staged = self._turn, self._stage(items, self._turn)
-        self._staged = None
+        indices, which, staged = self._ahead or (None, None, None)
+        self._ahead = None
+        if indices != tuple(i for i, _ in items):
+            which, staged = self._turn, self.pipe.stage(self._groups(items), self._turn)
         self._turn = 1 - which
-        engines = self.sets[which][:len(items)]
-        cur = torch.cuda.current_stream(self.dev)
-        cur.wait_stream(self.side)
-        self._fill_after = torch.cuda.Event()
-        self._fill_after.record(cur)
         tb = time.perf_counter()
-        if len(items) == 1:
-            engines[0].sample(staged[0][0], self.steps, *staged[0][1])
-        else:
-            DockEngine.sample_multi(engines, [s[0] for s in staged], self.steps, [s[1] for s in staged])
+        self.pipe.launch(staged, self.steps)
         t_ahead = 0.0
         if next_items:
             t0 = time.perf_counter()
-            self._staged = (tuple(i for i, _ in next_items), 1 - which, self._stage(next_items, 1 - which, ahead=True))
+            self._ahead = (tuple(i for i, _ in next_items), 1 - which, self.pipe.stage(self._groups(next_items), 1 - which, ahead=True))
             t_ahead = time.perf_counter() - t0
         torch.cuda.synchronize(self.dev)
         tc = time.perf_counter()
-        confs = [None] * len(items)
+        confs = [None] * len(staged)
         if self.ceng is not None:
-            from .engine import ConfidenceEngine
-            for k0 in range(0, len(items), len(self.cengs)):      # cbd_conf_score_multi: bitwise the results of separate score() calls
-                part = range(k0, min(k0 + len(self.cengs), len(items)))
-                for ce, k in zip(self.cengs, part):
-                    ce.set_complex(self.prepared[items[k][0]][0])
-                got = ConfidenceEngine.score_multi(self.cengs[:len(part)], [staged[k][0] for k in part], self.conf_args.crop_beyond)
-                for k, (c, _) in zip(part, got):
-                    confs[k] = c
+            confs = score_wave(self.cengs, [(s.group.cplx, None, s.pos) for s in staged], self.conf_args.crop_beyond)
         out = []
-        for (i, _), (pos, _), conf in zip(items, staged, confs):
-            res = {"complex": i}
+        for s, conf in zip(staged, confs):
+            res = {"complex": s.group.first}
             if conf is not None:
                 order = torch.argsort(conf, descending=True, stable=True)
                 best = int(order[0])
-                res.update(confidence=float(conf[best]), best=best, pos=pos[best].cpu().numpy(), order=order.cpu().numpy())
+                res.update(confidence=float(conf[best]), best=best, pos=s.pos[best].cpu().numpy(), order=order.cpu().numpy())
             else:
-                res.update(confidence=None, best=0, pos=pos[0].cpu().numpy())
+                res.update(confidence=None, best=0, pos=s.pos[0].cpu().numpy())
             if self.keep_poses:
-                res["all_pos"] = pos.cpu()
+                res["all_pos"] = s.pos.cpu()
             out.append(res)
         td = time.perf_counter()
         self.times["setup"] += tb - ta + t_ahead       # the part spent ahead ran under the step loop (inside "sample" as well)

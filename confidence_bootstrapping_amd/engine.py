@@ -336,6 +336,16 @@ class DockEngine:
         """Use `other`'s device-resident weights (one copy in HBM/L2) instead of uploading this engine's own."""
         _check(self.lib.cbd_share_weights(self.h, other.h))
 
+    def partner(self):
+        """A further engine of this engine's whole configuration that uses ITS device-resident weights and holds its own complex /
+        workspace: what cbd_sample_multi advances beside it."""
+        c = self.cfg
+        e = DockEngine(self.device, max_batch=c.max_batch, lm_embedding_dim=c.lm_embedding_dim, no_torsion=bool(c.no_torsion),
+                       lig_max_radius=c.lig_max_radius, rec_max_radius=c.rec_max_radius, cross_max_distance=c.cross_max_distance,
+                       center_max_distance=c.center_max_distance)
+        e.share_weights_from(self)
+        return e
+
     def sample_pair(self, other: "DockEngine", pos, steps, noise, other_pos, other_noise):
         """In-place reverse diffusion of two batches (two complexes) in lockstep with merged tensor-product launches
         (cbd_sample_pair).  noise / other_noise: (tr, rot, tor) device tensors or None."""

@@ -26,20 +26,23 @@ confidences with NaN -> -1000 like the reference.
 from __future__ import annotations
 
 import contextlib
+from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 from scipy.spatial.transform import Rotation as R
 
-from .engine import DockEngine, make_steps, complex_fingerprint, _single_complex, _single_all_atom_complex
+from .engine import make_steps, complex_fingerprint, _single_complex, _single_all_atom_complex
 from .hostcfg import with_glue_threads
-
+from .wave_pipeline import Group, LoaderBatch, WavePipeline, plan_waves, score_wave, switch_on_async_setup
 
 
 # Test hook (tests/test_gpu_finetune_loop.py, tools/check_upload_ordering.py): False removes the ordering of the pipelined side-stream fills
 # behind the caller's stream -- the state before round 6 -- to show that the hazard of ADVICE round 5 is real.  Never switched off in use.
+# Read by every sampling() call and handed to its wave_pipeline.WavePipeline, where the ordering lives.
 _ORDER_SIDE_FILLS = True
-_STEPS_CACHE = __import__("weakref").WeakKeyDictionary()       # model -> {schedule / flag key: engine.make_steps(...)} (see sampling())
+_STEPS_CACHE = __import__("weakref").WeakKeyDictionary()       # model -> {schedule / flag / embedding key: engine.make_steps(...)} (_cached_steps)
 
 def _mask_rotate_of(graph):
     mr = graph["ligand"].mask_rotate
@@ -423,6 +426,205 @@ def _sample_svgd(eng, cplx, pos, steps, noise, sched, cfg, n_total):
         pos.copy_(eng.modify_conformer(pos, tr_p, rot_p, tor_p))
 
 
+def _check_arguments(N, model, model_args, conf_model, filtering_data_list, inference_steps, schedules, t_schedule, asyncronous_noise_schedule,
+                     record, n_streams, svgd, ode, no_random, temp_sampling, pivot, return_features):
+    """What sampling() refuses, before it touches an engine -> (does the model embed the common time, the three schedules as float64)"""
+    assert not (return_features or pivot), "Not implemented yet in new inference version"
+    score_crop = getattr(model_args, "crop_beyond", None)
+    if record:
+        why = ("n_streams > 1" if n_streams > 1 else "SVGD sampling" if svgd is not None
+               else "the score model's crop_beyond" if score_crop is not None else None)
+        if why is not None:
+            raise NotImplementedError(f"return_full_trajectory is recorded by the one-launch step loop of a single engine; {why} "
+                                      "steps on the host or over several streams and does not record")
+    if svgd is not None:
+        if ode or no_random:
+            raise ValueError("SVGD sampling needs the stochastic sampler (the reference's SVGD branch reads the drawn noise)")
+        if not all(float(x) == 1.0 for x in (temp_sampling if np.iterable(temp_sampling) else [temp_sampling])):
+            raise NotImplementedError("SVGD together with low-temperature sampling: the reference's SVGD branch overwrites the temperature terms")
+    # asyncronous_noise_schedule (inference.py:384-388, utils/diffusion_utils.py:172-175): the caller passes the common time grid as
+    # `t_schedule`, the three component schedules are its beta-quantile images; what the flag changes is which time the MODEL embeds,
+    # and that is a property of the model (score_model.py:85) -- a model built without it ignores complex_t['t'] in the reference too
+    model_async = bool(getattr(getattr(model, "module", model), "asyncronous_noise_schedule", False))
+    if model_async and (t_schedule is None or not asyncronous_noise_schedule):
+        raise KeyError("'t': the model embeds the common diffusion time (asyncronous_noise_schedule) -- pass t_schedule and "
+                       "asyncronous_noise_schedule=True, as inference.py does")
+    if t_schedule is not None and len(t_schedule) != inference_steps:
+        raise ValueError("t_schedule length != inference_steps")
+    if score_crop is not None and getattr(model_args, "all_atoms", False):
+        raise NotImplementedError("score-model crop_beyond is supported for the C-alpha score model (the shipped architecture)")
+    if conf_model is not None and not hasattr(conf_model, "atom_confidence_predictor"):
+        raise NotImplementedError("confidence scoring runs on the all-atom confidence engine (all_atom_score_model)")
+    if filtering_data_list is not None and len(filtering_data_list) != N:
+        raise ValueError("filtering_data_list must have one graph per pose")
+    schedules = tuple(np.asarray(s, dtype=np.float64) for s in schedules)
+    if not all(len(s) == inference_steps for s in schedules):
+        raise ValueError("schedule length != inference_steps")
+    return model_async, schedules
+
+
+def _cached_steps(model, model_args, tr_schedule, rot_schedule, tor_schedule, common, ode=False, no_random=False, no_final_step_noise=False,
+                  temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5):
+    """engine.make_steps(...) through a cache.  --different_schedules (inference.py:375-383): rot / tor run on their own time grids;
+    everything schedule-dependent is a host scalar of the step, the engine itself is agnostic.  The per-step scalars are a pure function
+    of the schedules, six sigma limits, a few flags and the model's timestep embedding, and cost ~4 ms of host arithmetic (20 steps x
+    torch scalar ops in the reference's own dtypes) -- 2 % of a one-complex call in the reference's inference.py loop, where every call
+    passes the same schedules: cached per model, eight entries, the oldest evicted."""
+    tkey = lambda v: tuple(float(x) for x in v) if np.iterable(v) else float(v)
+    skey = (tr_schedule.tobytes(), rot_schedule.tobytes(), tor_schedule.tobytes(), None if common is None else common.tobytes(),
+            tuple(float(getattr(model_args, k)) for k in ("tr_sigma_min", "tr_sigma_max", "rot_sigma_min", "rot_sigma_max", "tor_sigma_min", "tor_sigma_max")),
+            bool(ode), bool(no_random), bool(no_final_step_noise), tkey(temp_sampling), tkey(temp_psi), float(temp_sigma_data),
+            model.timestep_emb_func)        # the function itself, not its id(): the key keeps it alive, so no later one can take its place
+    cache = _STEPS_CACHE.setdefault(model, {})          # beside the model, not on it: copy.deepcopy(model) must not meet ctypes arrays
+    steps = cache.get(skey)
+    if steps is None:
+        steps = make_steps(tr_schedule, model_args, model.timestep_emb_func, ode=ode, no_random=no_random,
+                           no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling, temp_psi=temp_psi,
+                           temp_sigma_data=temp_sigma_data, rot_schedule=rot_schedule, tor_schedule=tor_schedule, common_t_schedule=common)
+        if len(cache) >= 8:
+            cache.pop(next(iter(cache)))
+        cache[skey] = steps
+    return steps
+
+
+def _co_count(co_schedule, data_list, batch_size, n_streams=1, score_crop=None, svgd=None):
+    """how many complexes advance in lockstep (the groups of a wave)"""
+    if co_schedule is None:
+        # aim at ~160 poses per merged launch -- 4 complexes of 40 samples, 8 of 8 (measured: 8-way is +6 % over 4-way at 8 samples per
+        # complex and -1 % at 40).  Poses per complex = the leading run of equal names (the loader batches of a complex are merged).
+        name0 = getattr(data_list[0], "name", None) if len(data_list) else None
+        per = next((i for i, d in enumerate(data_list) if getattr(d, "name", None) != name0), len(data_list)) if name0 is not None else int(batch_size)
+        co_schedule = -(-160 // max(per, 1))
+    if svgd is not None and score_crop is not None:
+        raise NotImplementedError("SVGD together with the score model's crop_beyond")
+    # one complex at a time: over several streams; with crop_beyond, where the cropped receptor differs from pose to pose and step to
+    # step (_sample_cropped); with SVGD, where the samples of ONE complex interact, step by step on the host (_sample_svgd)
+    alone = n_streams != 1 or score_crop is not None or svgd is not None
+    return 1 if alone else max(1, min(int(co_schedule), 8))
+
+
+def _walk(data_list, batch_size, max_batch, n_co, no_torsion, S, noise, use_noise, no_final_step_noise):
+    """`data_list` in loader batches of `batch_size` -> the waves of wave_pipeline.Group that run together (wave_pipeline.plan_waves).
+    The reference collates every chunk with torch_geometric's Batch (utils/sampling.py:78); only the ligand coordinates of the poses and
+    ONE copy of the complex are needed here, so the chunks are walked without collating (for a 40-pose complex the collation of the
+    1281-wide receptor features alone costs more host time than the GPU work).  The noise of a chunk is drawn (or sliced from `noise`)
+    as the walk reaches it: the order of the draws on the global generator is the reference's."""
+    batches, keys, offset = [], [], 0
+    for start in range(0, len(data_list), max(int(batch_size), 1)):
+        chunk = data_list[start:start + max(int(batch_size), 1)]
+        b = len(chunk)
+        if b > max_batch:
+            raise RuntimeError(f"batch of {b} exceeds the engine capacity {max_batch}")
+        if any(getattr(d, "num_graphs", 1) != 1 for d in chunk):
+            raise ValueError("data_list elements must be single graphs (as inference.py builds them)")
+        batch = chunk[0]
+        Nl = batch["ligand"].pos.shape[0]
+        key = complex_fingerprint(batch)
+        for d in chunk[1:]:
+            if complex_fingerprint(d) != key:
+                raise NotImplementedError("all poses of one batch must belong to the same complex (as modify_conformer_batch assumes)")
+        R_ = int(batch["ligand"].edge_mask.sum()) if not no_torsion else 0
+        z = (None, None, None)
+        if use_noise and noise is not None:
+            z = (noise["tr"][:, offset:offset + b], noise["rot"][:, offset:offset + b],
+                 noise["tor"][:, offset * R_:(offset + b) * R_] if R_ > 0 else None)
+        elif use_noise:
+            z = _draw_chunk_noise(b, R_, S, no_final_step_noise)
+        lig_pos = torch.stack([d["ligand"].pos.detach().cpu().float().reshape(Nl, 3) for d in chunk])
+        batches.append(LoaderBatch(offset, lig_pos, z, batch))
+        keys.append(key)
+        offset += b
+    plan = plan_waves(keys, [b.pos.shape[0] for b in batches], max_batch, n_co)
+    return [[Group(_single_complex(batches[g[0]].graph)[0], keys[g[0]], [batches[c] for c in g]) for g in wave] for wave in plan]
+
+
+@contextlib.contextmanager
+def _call_scope():
+    """End-of-call duties of sampling().  The pipelined set-up is a property of THIS call, not of the model's cached engines:
+    "async_setup" goes back to what it was.  The confidence engine's capacity flag is sticky and lives on the (cached) engine: if the
+    call ends by an exception before the final check(), the flag must not survive into the next, unrelated call.
+    -> scope.async_before: engines whose "async_setup" this call switched on -> previous value; scope.conf_used: the confidence
+    engines this call scored on"""
+    scope = SimpleNamespace(async_before={}, conf_used=set())
+    try:
+        yield scope
+    except BaseException:
+        for ceng in scope.conf_used:
+            try:
+                ceng.check()
+            except RuntimeError:
+                pass
+        raise
+    finally:
+        for e, was in scope.async_before.items():
+            e.set_option("async_setup", was)
+
+
+def _engine_sets(model, eng, waves, look_ahead, scope):
+    """The two engine sets the waves alternate between (the same set twice without look-ahead): `eng` and as many partners sharing its
+    weights as the widest wave of each parity needs, running with `eng`'s options (operand precision, graph replay, ...)."""
+    need_a = max((len(w) for w in waves[0::2]), default=1)
+    need_b = max((len(w) for w in waves[1::2]), default=0) if look_ahead else 0
+    partners = model.co_engines(need_a - 1 + need_b, eng) if need_a - 1 + need_b > 0 else []
+    for e in partners:
+        for name, val in getattr(eng, "_options", {}).items():
+            if name != "async_setup" and e.get_option(name) != val:
+                e.set_option(name, val)
+    if need_b:
+        switch_on_async_setup([eng] + partners, scope.async_before)
+    set_a = [eng] + partners[:need_a - 1]
+    return [set_a, partners[need_a - 1:] if need_b else set_a]
+
+
+def _score_confidence(staged, conf_model, max_batch, filtering_data_list, crop, used, out):
+    """Confidence [b] of every group's final poses, appended to `out`, on the confidence model's engine and its partners: the k-th
+    complex of a launch runs on the k-th of them.  `filtering_data_list`: the all-atom graphs per pose (None: the sampled graphs
+    carry the 'atom' stores).  No host sync: the engines go into `used`, sampling() checks their sticky capacity flags at the end."""
+    main = conf_model.engine(max_batch=max_batch)      # looked up here, behind the wave's launch: the look-up checksums weights on the device
+    items = []
+    for s in staged:
+        fbatch = filtering_data_list[s.group.first] if filtering_data_list is not None else s.group.batches[0].graph
+        fg, _, fNl = _single_all_atom_complex(fbatch)
+        if fNl != s.pos.shape[1]:
+            raise RuntimeError("filtering graphs hold a different ligand than the sampled ones")
+        items.append((fg, complex_fingerprint(fbatch) + (fg["atom"].pos.shape[0],), s.pos))
+    n = min(len(items), 4)
+    cengs = [main] + (conf_model.co_engines(n - 1, main) if n > 1 else [])
+    used.update(cengs)
+    out.extend(score_wave(cengs, items, crop, check=False, skip_same_key=True))
+
+
+def _finish_wave(staged, trajs, data_list, trajectory, score=None):
+    """the wave's results back into the caller's lists: recorded frames (one download for the wave: the groups' [S,b,Nl,3] blocks back
+    to back), final poses (views of the device batch), confidences (`score`: _score_confidence with the call's constants bound)"""
+    if trajs is not None:
+        host = torch.cat([t.reshape(-1) for t in trajs]).cpu()
+        lo = 0
+        for s, t in zip(staged, trajs):
+            block = host[lo:lo + t.numel()].reshape(t.shape)
+            lo += t.numel()
+            first = s.group.first
+            for i in range(s.pos.shape[0]):
+                trajectory[first + i] = block[:, i].clone()
+    for s in staged:
+        first, B, Nl = s.group.first, s.pos.shape[0], s.pos.shape[1]
+        flat = s.pos.reshape(B * Nl, 3)
+        for i in range(B):
+            data_list[first + i]["ligand"].pos = flat[i * Nl:(i + 1) * Nl]
+    if score is not None:
+        score(staged)
+
+
+def _run_waves(pipe, waves, finish, look_ahead, **launch_kw):
+    """launch k, stage k + 1 on the other engine set under its step loop (`look_ahead`; otherwise after finish k), finish k"""
+    ahead = None
+    for k, wave in enumerate(waves):
+        staged = ahead if ahead is not None else pipe.stage(wave, k % 2, ahead=k > 0, skip_same_key=True)
+        trajs = pipe.launch(staged, **launch_kw)
+        ahead = pipe.stage(waves[k + 1], (k + 1) % 2, ahead=True, skip_same_key=True) if look_ahead and k + 1 < len(waves) else None
+        finish(staged, trajs)
+
+
 @with_glue_threads
 def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_schedule, device, t_to_sigma, model_args,
              no_random=False, ode=False, visualization_list=None, confidence_model=None, filtering_data_list=None,
@@ -444,317 +646,55 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     (cbd_sample_traj) and they are downloaded once per co-scheduled wave.  With a `visualization_list` every frame is added as
     add(frame + original_center, part=1, order=k + 2) -- what the reference's commented-out per-step add intended -- in place of the
     single final order=2 frame.  Not implemented (NotImplementedError) for the host-stepped, non-default samplers: n_streams > 1,
-    SVGD and the score model's crop_beyond."""
-    N = len(data_list)
-    assert not (return_features or pivot), "Not implemented yet in new inference version"
-    record = bool(return_full_trajectory)
-    if record:
-        svgd_on = svgd_weight_log_0 is not None and svgd_weight_log_1 is not None
-        why = ("n_streams > 1" if n_streams > 1 else "SVGD sampling" if svgd_on
-               else "the score model's crop_beyond" if getattr(model_args, "crop_beyond", None) is not None else None)
-        if why is not None:
-            raise NotImplementedError(f"return_full_trajectory is recorded by the one-launch step loop of a single engine; {why} "
-                                      "steps on the host or over several streams and does not record")
-    trajectory = [None] * N
+    SVGD and the score model's crop_beyond.
+    The waves (co-scheduled groups of complexes) run on wave_pipeline.WavePipeline: the next wave is set up under the current one."""
+    N, S, record = len(data_list), inference_steps, bool(return_full_trajectory)
     svgd = None
     if svgd_weight_log_0 is not None and svgd_weight_log_1 is not None:
-        if ode or no_random:
-            raise ValueError("SVGD sampling needs the stochastic sampler (the reference's SVGD branch reads the drawn noise)")
-        if not all(float(x) == 1.0 for x in (temp_sampling if np.iterable(temp_sampling) else [temp_sampling])):
-            raise NotImplementedError("SVGD together with low-temperature sampling: the reference's SVGD branch overwrites the temperature terms")
         svgd = dict(weight_log_0=svgd_weight_log_0, weight_log_1=svgd_weight_log_1, repulsive_weight_log_0=svgd_repulsive_weight_log_0,
                     repulsive_weight_log_1=svgd_repulsive_weight_log_1, kernel_size_log_0=svgd_kernel_size_log_0,
                     kernel_size_log_1=svgd_kernel_size_log_1, langevin_weight_log_0=svgd_langevin_weight_log_0,
                     langevin_weight_log_1=svgd_langevin_weight_log_1, rot_log_rel_weight=svgd_rot_log_rel_weight,
                     tor_log_rel_weight=svgd_tor_log_rel_weight, use_x0=bool(svgd_use_x0))
-    # asyncronous_noise_schedule (inference.py:384-388, utils/diffusion_utils.py:172-175): the caller passes the common time grid as
-    # `t_schedule`, the three component schedules are its beta-quantile images; what the flag changes is which time the MODEL embeds,
-    # and that is a property of the model (score_model.py:85) -- a model built without it ignores complex_t['t'] in the reference too
-    model_async = bool(getattr(getattr(model, "module", model), "asyncronous_noise_schedule", False))
-    if model_async and (t_schedule is None or not asyncronous_noise_schedule):
-        raise KeyError("'t': the model embeds the common diffusion time (asyncronous_noise_schedule) -- pass t_schedule and "
-                       "asyncronous_noise_schedule=True, as inference.py does")
-    if t_schedule is not None and len(t_schedule) != inference_steps:
-        raise ValueError("t_schedule length != inference_steps")
-    score_crop = getattr(model_args, "crop_beyond", None)
-    if score_crop is not None and getattr(model_args, "all_atoms", False):
-        raise NotImplementedError("score-model crop_beyond is supported for the C-alpha score model (the shipped architecture)")
     conf_model = getattr(confidence_model, "module", confidence_model)
-    if conf_model is not None and not hasattr(conf_model, "atom_confidence_predictor"):
-        raise NotImplementedError("confidence scoring runs on the all-atom confidence engine (all_atom_score_model)")
-    if filtering_data_list is not None and len(filtering_data_list) != N:
-        raise ValueError("filtering_data_list must have one graph per pose")
-    confidence = []
-    tr_schedule, rot_schedule, tor_schedule = (np.asarray(s, dtype=np.float64) for s in (tr_schedule, rot_schedule, tor_schedule))
-    if not (len(tr_schedule) == len(rot_schedule) == len(tor_schedule) == inference_steps):
-        raise ValueError("schedule length != inference_steps")
+    model_async, schedules = _check_arguments(N, model, model_args, conf_model, filtering_data_list, inference_steps,
+                                              (tr_schedule, rot_schedule, tor_schedule), t_schedule, asyncronous_noise_schedule, record,
+                                              n_streams, svgd, ode, no_random, temp_sampling, pivot, return_features)
     device = torch.device(device)
     model = getattr(model, "module", model)
+    score_crop = getattr(model_args, "crop_beyond", None)
     eng = model.engine_pool(n_streams=n_streams, max_batch=max(int(batch_size), 1)) if n_streams > 1 else model.engine()
-    # --different_schedules (inference.py:375-383): rot / tor run on their own time grids; everything schedule-dependent is a host
-    # scalar of the step (engine.make_steps), the engine itself is agnostic
-    # The per-step scalars are a pure function of the schedules, six sigma limits and a few flags, and cost ~4 ms of host arithmetic
-    # (20 steps x torch scalar ops in the reference's own dtypes) -- 2 % of a one-complex call in the reference's inference.py loop, where
-    # every call passes the same schedules: cached on the model (its timestep embedding is part of the result), eight entries.
-    common = np.asarray(t_schedule, dtype=np.float64) if model_async else None
-    tkey = lambda v: tuple(float(x) for x in v) if np.iterable(v) else float(v)
-    skey = (tr_schedule.tobytes(), rot_schedule.tobytes(), tor_schedule.tobytes(), None if common is None else common.tobytes(),
-            tuple(float(getattr(model_args, k)) for k in ("tr_sigma_min", "tr_sigma_max", "rot_sigma_min", "rot_sigma_max", "tor_sigma_min", "tor_sigma_max")),
-            bool(ode), bool(no_random), bool(no_final_step_noise), tkey(temp_sampling), tkey(temp_psi), float(temp_sigma_data))
-    cache = _STEPS_CACHE.setdefault(model, {})          # beside the model, not on it: copy.deepcopy(model) must not meet ctypes arrays
-    steps = cache.get(skey)
-    if steps is None:
-        steps = make_steps(tr_schedule, model_args, model.timestep_emb_func, ode=ode, no_random=no_random,
-                           no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling, temp_psi=temp_psi,
-                           temp_sigma_data=temp_sigma_data, rot_schedule=rot_schedule, tor_schedule=tor_schedule, common_t_schedule=common)
-        if len(cache) >= 8:
-            cache.pop(next(iter(cache)))
-        cache[skey] = steps
-    S = inference_steps
-    use_noise = not (no_random or ode)
-    if co_schedule is None:
-        # aim at ~160 poses per merged launch -- 4 complexes of 40 samples, 8 of 8 (measured: 8-way is +6 % over 4-way at 8 samples per
-        # complex and -1 % at 40).  Poses per complex = the leading run of equal names (the loader batches of a complex are merged).
-        name0 = getattr(data_list[0], "name", None) if N else None
-        per = next((i for i, d in enumerate(data_list) if getattr(d, "name", None) != name0), N) if name0 is not None else int(batch_size)
-        co_schedule = -(-160 // max(per, 1))
-    n_co = max(1, min(int(co_schedule), 8)) if n_streams == 1 else 1
-    if score_crop is not None:
-        n_co = 1            # the cropped receptor differs from pose to pose and step to step: one complex at a time (_sample_cropped)
+    steps = _cached_steps(model, model_args, *schedules, np.asarray(t_schedule, dtype=np.float64) if model_async else None, ode, no_random,
+                          no_final_step_noise, temp_sampling, temp_psi, temp_sigma_data)
+    n_co = _co_count(co_schedule, data_list, batch_size, n_streams, score_crop, svgd)
+    # the host-stepped samplers (and a CPU device) run their waves one after the other, without a side stream
+    look_ahead = svgd is None and score_crop is None and n_streams == 1 and device.type == "cuda"
+    host_step = None
     if svgd is not None:
-        if score_crop is not None:
-            raise NotImplementedError("SVGD together with the score model's crop_beyond")
-        n_co = 1            # the samples of ONE complex interact: step by step on the host (_sample_svgd)
-    offset = 0
-    pending = []          # (first pose index, b, pos [b,Nl,3] CPU, z_tr, z_rot, z_tor, loader batch)
-    pending_key = None
-
-    groups = []           # closed groups (one complex each) waiting to be advanced together
-    waves = []            # lists of <= n_co groups, in order: each is ONE co-scheduled call
-    conf_engines_used = set()
-
-    def flush():
-        """close the pending group (consecutive loader batches of one complex); `n_co` closed groups make a wave"""
-        nonlocal pending, pending_key
-        if not pending:
-            return
-        groups.append((pending, pending_key))
-        pending, pending_key = [], None
-        if len(groups) >= n_co:
-            waves.append(list(groups))
-            groups.clear()
-
-    # Set-up of the NEXT wave under the step loop of the current one: two alternating sets of engines (the partners share the main
-    # engine's weights), cbd_set_complex on a stream of its own ("async_setup": it waits for the launches of ITS engine only), the
-    # pose / noise uploads on a side stream.  The host is free for that as soon as the graph launch of the current wave returns.
-    plain = svgd is None and score_crop is None and n_streams == 1 and device.type == "cuda"
-    side = torch.cuda.Stream(device) if plain else None
-    sets = None
-    # Ordering of the side-stream fills (ADVICE round 5): their device buffers come from the CURRENT stream's allocator pool, and a block
-    # the host has freed may still be read by work already queued there (e.g. the confidence kernels of the previous wave).  `fill_after`
-    # is an event on the current stream recorded just BEFORE a wave is launched: the fills of the next wave follow everything queued up to
-    # it, but not the running wave itself.  Wave 0 (nothing of ours is running yet) simply follows the current stream.
-    fill_after = [None]
-    async_before = {}       # engines whose "async_setup" this call switched on -> previous value (restored on exit)
-
-    def engine_sets():
-        nonlocal sets
-        if sets is None:
-            need_a = max((len(w) for w in waves[0::2]), default=1)
-            need_b = max((len(w) for w in waves[1::2]), default=0) if plain else 0
-            partners = model.co_engines(need_a - 1 + need_b, eng) if need_a - 1 + need_b > 0 else []
-            set_a = [eng] + partners[:need_a - 1]
-            sets = [set_a, partners[need_a - 1:] if need_b else set_a]
-            for e in partners:      # partners run with the main engine's options (operand precision, graph replay, ...)
-                for name, val in getattr(eng, "_options", {}).items():
-                    if name != "async_setup" and e.get_option(name) != val:
-                        e.set_option(name, val)
-            if need_b:
-                for e in [eng] + partners:
-                    was = e.get_option("async_setup", 0)
-                    if was != 1:
-                        async_before[e] = was
-                        e.set_option("async_setup", 1)
-        return sets
-
-    def prepare_wave(k):
-        """per-complex set-up (graph upload, receptor embedding) and the uploads of wave k on engine set k % 2.  Device tensors are
-        allocated from the CURRENT stream's pool (whatever it hands out was last used before the running wave was launched) and
-        only filled on the side stream: an allocation on the side stream would wait for the running wave (caching-allocator events)."""
-        engines = engine_sets()[k % 2]
-        ctx = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
-        if side is not None and _ORDER_SIDE_FILLS:
-            if fill_after[0] is None:
-                side.wait_stream(torch.cuda.current_stream(device))
-            else:
-                side.wait_event(fill_after[0])
-
-        def up(t):
-            if not plain:
-                return t                  # the other samplers take host noise
-            t = t.to(torch.float32).contiguous()
-            d = torch.empty(t.shape, dtype=torch.float32, device=device)
-            with ctx():
-                d.copy_(t, non_blocking=True)
-            return d
-        work = []
-        for (pend, key), e in zip(waves[k], engines):
-            batch0 = pend[0][6]           # first graph of the group: all of them are poses of the same complex
-            g, _, _ = _single_complex(batch0)
-            if e.complex_key != key:
-                e.set_complex(g, key)
-            R_ = e.R if not model_args.no_torsion else 0
-            pos_h = torch.cat([p[2] for p in pend], dim=0)
-            pos = up(pos_h) if plain else pos_h.to(device, torch.float32).contiguous()
-            cat = lambda i, dim: None if pend[0][i] is None else up(torch.cat([p[i] for p in pend], dim=dim))
-            work.append((pend, e, pos, (cat(3, 1), cat(4, 1), cat(5, 1) if R_ > 0 else None), batch0, key))
-        return work
-
-    def launch_wave(work):
-        """Up to eight complexes advance in lockstep (cbd_sample_multi: their tensor-product launches are merged, so a launch
-        carries several times the waves -- +24 % poses/s at 8 samples per complex); one group runs on cbd_sample.  Results are
-        bitwise those of separate calls (tests/test_gpu_parity.py::test_sample_pair_equals_two_samples)."""
-        if side is not None:
-            cur = torch.cuda.current_stream(device)
-            cur.wait_stream(side)
-            fill_after[0] = torch.cuda.Event()
-            fill_after[0].record(cur)
-        if svgd is not None:
-            for _, e, pos, nz, batch0, _ in work:
-                _sample_svgd(e, _single_complex(batch0)[0], pos, steps, nz, (tr_schedule, rot_schedule, tor_schedule), svgd, N)
-        elif score_crop is not None:
-            for _, e, pos, nz, batch0, key in work:
-                _sample_cropped(e, _single_complex(batch0)[0], key, pos, steps, nz, float(score_crop))
-        elif len(work) == 1:
-            t = work[0][1].sample(work[0][2], steps, *work[0][3], trajectory=record)
-            return [t] if record else None
-        else:
-            t = DockEngine.sample_multi([w[1] for w in work], [w[2] for w in work], steps, [w[3] for w in work], trajectory=record)
-            return t if record else None
-
-    def finish_wave(work, trajs=None):
-        if trajs is not None:          # one download for the wave: the groups' [S,b,Nl,3] blocks back to back
-            host = torch.cat([t.reshape(-1) for t in trajs]).cpu()
-            lo = 0
-            for (pend, _, pos, _, _, _), t in zip(work, trajs):
-                block = host[lo:lo + t.numel()].reshape(t.shape)
-                lo += t.numel()
-                for i in range(pos.shape[0]):
-                    trajectory[pend[0][0] + i] = block[:, i].clone()
-        # Confidence of the wave's final poses: up to four complexes per set of fused-conv launches (cbd_conf_score_multi: a launch then
-        # covers ~4x the waves and its last, partly filled round of resident waves costs ~1 % instead of ~6 %).  No host sync per
-        # complex: the capacity flag of a confidence engine is sticky and checked once at the end.
-        from .engine import ConfidenceEngine
-        scored = []          # (confidence engine, poses, crop) waiting to be scored together
-
-        def score_waiting():
-            if scored:
-                for c, _ in ConfidenceEngine.score_multi([p[0] for p in scored], [p[1] for p in scored], scored[0][2], check=False):
-                    confidence.append(c)
-                scored.clear()
-        cmain = conf_model.engine(max_batch=eng.max_batch) if conf_model is not None else None
-        for pend, e, pos, _, batch0, _ in work:
-            first, B, Nl = pend[0][0], pos.shape[0], pos.shape[1]
-            flat = pos.reshape(B * Nl, 3)
-            for i in range(B):
-                data_list[first + i]["ligand"].pos = flat[i * Nl:(i + 1) * Nl]
+        host_step = lambda s: _sample_svgd(s.engine, s.group.cplx, s.pos, steps, s.noise, schedules, svgd, N)
+    elif score_crop is not None:
+        host_step = lambda s: _sample_cropped(s.engine, s.group.cplx, s.group.key, s.pos, steps, s.noise, float(score_crop))
+    trajectory, confidence = [None] * N, []
+    with torch.no_grad(), _call_scope() as scope:
+        waves = _walk(data_list, batch_size, eng.max_batch, n_co, model_args.no_torsion, S, noise, not (no_random or ode), no_final_step_noise)
+        if waves:
+            score = None
             if conf_model is not None:
-                if filtering_data_list is not None:
-                    fbatch = filtering_data_list[first]
-                    crop = getattr(filtering_model_args, "crop_beyond", None)
-                else:
-                    fbatch, crop = batch0, None
-                fg, _, fNl = _single_all_atom_complex(fbatch)
-                if fNl != Nl:
-                    raise RuntimeError("filtering graphs hold a different ligand than the sampled ones")
-                # the k-th complex of a group gets the k-th confidence engine (cbd_conf_score_multi takes one engine per complex)
-                k = len(scored)
-                ceng = cmain if k == 0 else conf_model.co_engines(k, cmain)[k - 1]
-                ckey = complex_fingerprint(fbatch) + (fg["atom"].pos.shape[0],)
-                if ceng.complex_key != ckey:
-                    ceng.set_complex(fg, ckey)
-                scored.append((ceng, pos, crop))
-                conf_engines_used.add(ceng)
-                if len(scored) == 4:
-                    score_waiting()
-        score_waiting()
+                crop = getattr(filtering_model_args, "crop_beyond", None) if filtering_data_list is not None else None
+                score = partial(_score_confidence, conf_model=conf_model, max_batch=eng.max_batch, filtering_data_list=filtering_data_list,
+                                crop=crop, used=scope.conf_used, out=confidence)
+            pipe = WavePipeline(device, _engine_sets(model, eng, waves, look_ahead, scope), side_fills=look_ahead, order_fills=_ORDER_SIDE_FILLS)
+            _run_waves(pipe, waves, partial(_finish_wave, data_list=data_list, trajectory=trajectory, score=score), look_ahead,
+                       steps=steps, trajectory=record, host_step=host_step)
+        for idx, visualization in enumerate(visualization_list or []):
+            center = data_list[idx].original_center.detach().cpu()
+            if record:
+                for t_idx in range(S):
+                    visualization.add(trajectory[idx][t_idx] + center, part=1, order=t_idx + 2)
+            else:
+                visualization.add(data_list[idx]["ligand"].pos.detach().cpu() + center, part=1, order=2)
+    for ceng in scope.conf_used:
+        ceng.check()          # raises if any of the batches above exceeded a per-atom edge capacity
+    confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000) if conf_model is not None else None
+    return (data_list, confidence, trajectory) if record else (data_list, confidence)
 
-    def run_waves():
-        if groups:
-            waves.append(list(groups))
-            groups.clear()
-        work = prepare_wave(0) if waves else None
-        for k in range(len(waves)):
-            trajs = launch_wave(work)
-            ahead = prepare_wave(k + 1) if plain and k + 1 < len(waves) else None
-            finish_wave(work, trajs)
-            work = ahead if ahead is not None else (prepare_wave(k + 1) if k + 1 < len(waves) else None)
-
-    def drop_stale_capacity_flags(exc_type):
-        """The confidence engine's capacity flag is sticky and lives on the (cached) engine: if this call ends by an exception
-        before the final check(), the flag must not survive into the next, unrelated call."""
-        if exc_type is not None:
-            for ceng in conf_engines_used:
-                try:
-                    ceng.check()
-                except RuntimeError:
-                    pass
-
-    class _Guard:
-        def __enter__(self):
-            return self
-
-        def __exit__(self, exc_type, exc, tb):
-            drop_stale_capacity_flags(exc_type)
-            for e, was in async_before.items():      # the pipelined set-up is a property of THIS call, not of the model's cached engines
-                e.set_option("async_setup", was)
-            return False
-
-    with torch.no_grad(), _Guard():
-        # The reference collates every chunk with torch_geometric's Batch (utils/sampling.py:78); only the ligand coordinates of
-        # the poses and ONE copy of the complex are needed here, so the chunks are walked without collating (for a 40-pose
-        # complex the collation of the 1281-wide receptor features alone costs more host time than the GPU work).
-        for start in range(0, N, max(int(batch_size), 1)):
-            chunk = data_list[start:start + max(int(batch_size), 1)]
-            b = len(chunk)
-            if b > eng.max_batch:
-                raise RuntimeError(f"batch of {b} exceeds the engine capacity {eng.max_batch}")
-            if any(getattr(d, "num_graphs", 1) != 1 for d in chunk):
-                raise ValueError("data_list elements must be single graphs (as inference.py builds them)")
-            batch = chunk[0]
-            Nl = batch["ligand"].pos.shape[0]
-            key = complex_fingerprint(batch)
-            for d in chunk[1:]:
-                if complex_fingerprint(d) != key:
-                    raise NotImplementedError("all poses of one batch must belong to the same complex (as modify_conformer_batch assumes)")
-            if pending and (key != pending_key or sum(p[1] for p in pending) + b > eng.max_batch):
-                flush()
-            R_ = int(batch["ligand"].edge_mask.sum()) if not model_args.no_torsion else 0
-            z_tr = z_rot = z_tor = None
-            if use_noise:
-                if noise is not None:
-                    z_tr = noise["tr"][:, offset:offset + b]
-                    z_rot = noise["rot"][:, offset:offset + b]
-                    z_tor = noise["tor"][:, offset * R_:(offset + b) * R_] if R_ > 0 else None
-                else:
-                    z_tr, z_rot, z_tor = _draw_chunk_noise(b, R_, S, no_final_step_noise)
-            lig_pos = torch.stack([d["ligand"].pos.detach().cpu().float().reshape(Nl, 3) for d in chunk])
-            pending.append((offset, b, lig_pos, z_tr, z_rot, z_tor, batch))
-            pending_key = key
-            offset += b
-        flush()
-        run_waves()
-        if visualization_list is not None:
-            for idx, visualization in enumerate(visualization_list):
-                center = data_list[idx].original_center.detach().cpu()
-                if record:
-                    for t_idx in range(S):
-                        visualization.add(trajectory[idx][t_idx] + center, part=1, order=t_idx + 2)
-                else:
-                    visualization.add(data_list[idx]["ligand"].pos.detach().cpu() + center, part=1, order=2)
-    if conf_model is not None:
-        for ceng in conf_engines_used:
-            ceng.check()          # raises if any of the batches above exceeded a per-atom edge capacity
-        confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
-        return (data_list, confidence, trajectory) if record else (data_list, confidence)
-    return (data_list, None, trajectory) if record else (data_list, None)
