@@ -5,6 +5,8 @@ intra-ligand distance.  `performance_metrics`: the reference's aggregate diction
 selection rules, including the reference's own inconsistencies (e.g. the `reversefiltered_*centroid*` / `*self_intersect*`
 entries index with the DESCENDING confidence order, inference.py:782-785, 812-819) so that numbers are comparable run to run.
 Table-driven instead of the reference's 290 unrolled lines.
+`cluster_poses` / `cluster_poses_batch` (no reference counterpart): the distinct binding modes among the poses of a complex, on the host
+and on the GPU (`cbd_pose_modes`).
 """
 from __future__ import annotations
 
@@ -38,12 +40,36 @@ def pose_metrics(ligand_pos, orig_ligand_pos, mol=None, device=None):
 METRICS_MAX_ATOMS, METRICS_MAX_REF_ATOMS = 512, 4096      # capacity of cbd_pose_metrics per complex: N and Q * N (include/cbdock.h)
 
 
+def _iso_for_item(i, n, mol, given=None):
+    """(key, entry) of item i's isomorphisms for n atoms: `given` (idx1, idx2) as it is (not cached), else the cache entry of `mol`, else --
+    mol None, or an enumeration that raised, after the line the host route prints -- the identity mapping (K = 1)."""
+    from . import molecules_utils as mu
+    key = entry = None
+    if given is not None:
+        idx1, idx2 = (np.ascontiguousarray(np.asarray(x, dtype=np.int32)) for x in given)
+        if idx1.ndim != 2 or idx1.shape != idx2.shape or idx1.shape[0] < 1 or idx1.shape[1] != n:
+            raise ValueError(f"item {i}: isomorphism tables {idx1.shape} / {idx2.shape} for {n} atoms")
+        entry = {"iso": (idx1, idx2), "exc": None, "dev": {}, "bytes": 0}
+    elif mol is not None:
+        try:
+            key, entry = mu._iso_entry(*mu._graph_of(mol))
+            if entry["exc"] is not None:
+                raise entry["exc"][0](*entry["exc"][1])
+            if entry["iso"][0].shape[1] != n:
+                raise ValueError("coordinate / isomorphism shapes do not match")
+        except Exception as e:
+            print("Using non corrected RMSD because of the error:", e)
+            key = entry = None
+    if entry is None:
+        key, entry = mu._identity_entry(n)
+    return key, entry
+
+
 def _prepare_metrics_items(items, isomorphisms=None):
     """Host half of pose_metrics_batch, no GPU: per item the fp32 arrays, the sizes and the isomorphism cache entry.
     `items`: (ligand_pos [P, N, 3], orig_pos [Q, N, 3] or [N, 3], mol or None); `isomorphisms`: optional list, one (idx1, idx2) or None per
     item, used as given instead of the cache.  mol None, or an enumeration that raised: the identity mapping (K = 1), after the line the
     host route prints.  -> list of dicts lp, ref, mol, P, N, Q, K, key, entry, fits."""
-    from . import molecules_utils as mu
     out = []
     for i, (ligand_pos, orig_pos, mol) in enumerate(items):
         lp = np.ascontiguousarray(np.asarray(ligand_pos, dtype=np.float32))
@@ -52,25 +78,7 @@ def _prepare_metrics_items(items, isomorphisms=None):
         if lp.ndim != 3 or lp.shape[2] != 3 or ref.ndim != 3 or ref.shape[0] < 1 or ref.shape[1:] != lp.shape[1:]:
             raise ValueError(f"item {i}: poses {lp.shape} and crystal poses {ref.shape} do not match")
         n = lp.shape[1]
-        given = isomorphisms[i] if isomorphisms is not None else None
-        key = entry = None
-        if given is not None:
-            idx1, idx2 = (np.ascontiguousarray(np.asarray(x, dtype=np.int32)) for x in given)
-            if idx1.ndim != 2 or idx1.shape != idx2.shape or idx1.shape[0] < 1 or idx1.shape[1] != n:
-                raise ValueError(f"item {i}: isomorphism tables {idx1.shape} / {idx2.shape} for {n} atoms")
-            entry = {"iso": (idx1, idx2), "exc": None, "dev": {}, "bytes": 0}
-        elif mol is not None:
-            try:
-                key, entry = mu._iso_entry(*mu._graph_of(mol))
-                if entry["exc"] is not None:
-                    raise entry["exc"][0](*entry["exc"][1])
-                if entry["iso"][0].shape[1] != n:
-                    raise ValueError("coordinate / isomorphism shapes do not match")
-            except Exception as e:
-                print("Using non corrected RMSD because of the error:", e)
-                key = entry = None
-        if entry is None:
-            key, entry = mu._identity_entry(n)
+        key, entry = _iso_for_item(i, n, mol, isomorphisms[i] if isomorphisms is not None else None)
         out.append(dict(lp=lp, ref=ref, mol=mol, P=lp.shape[0], N=n, Q=ref.shape[0], K=entry["iso"][0].shape[0], key=key, entry=entry,
                         fits=1 <= n <= METRICS_MAX_ATOMS and ref.shape[0] * n <= METRICS_MAX_REF_ATOMS))
     return out
@@ -142,6 +150,148 @@ def pose_metrics_batch(items, device, isomorphisms=None):
         p1 = p0 + it["P"]
         results[i] = (f32[0, p0:p1].copy(), f32[1, p0:p1].copy(), f32[2, p0:p1].copy(), got[3, p0:p1].copy(), got[4, p0:p1].copy())
         p0 = p1
+    return results
+
+
+MODES_MAX_ATOMS, MODES_MAX_POSES = 512, 256      # capacity of cbd_pose_modes per group: N and P (include/cbdock.h)
+
+
+def pairwise_symmetry_rmsd(ligand_pos, idx1, idx2):
+    """float32 [P, P]: for i < j  D[i, j] = float32(sqrt(min_k sum_a |x_i[idx1[k, a]] - x_j[idx2[k, a]]|^2 / N)), the sums in fp64 on the fp32
+    coordinates; D[j, i] = D[i, j] from the same value, the diagonal 0; the row and the column (diagonal included) of a pose with a
+    coordinate that is not finite are NaN.  The definition of cbd_pose_modes' matrix, on the host."""
+    lp = np.asarray(ligand_pos, dtype=np.float32).astype(np.float64)
+    P, N = lp.shape[:2]
+    idx1, idx2 = np.asarray(idx1), np.asarray(idx2)
+    best = np.full((P, P), np.inf)
+    step = max(1, (1 << 22) // max(P * P * N * 3, 1))          # isomorphisms per pass: about 32 MB of differences
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(0, idx1.shape[0], step):
+            a = lp[:, idx1[k:k + step]]                            # [P, k, N, 3]
+            b = lp[:, idx2[k:k + step]]
+            best = np.minimum(best, ((a[:, None] - b[None]) ** 2).sum(axis=(3, 4)).min(axis=2))
+        d = np.sqrt(best / N).astype(np.float32)
+    d = np.triu(d, 1)
+    d = d + d.T
+    bad = ~np.isfinite(lp).all(axis=(1, 2))
+    d[bad, :] = np.nan
+    d[:, bad] = np.nan
+    return d
+
+
+def modes_from_matrix(matrix, cutoff=2.0):
+    """Leader clustering in rank order on a pose-against-pose matrix [P, P]: pose p joins the best-ranked existing head h with
+    matrix[h, p] <= cutoff, else it becomes a head.  Only heads are compared against: a pose near a member but far from that member's head
+    opens a new mode.  A pose whose diagonal entry is NaN gets -1 and is never a head.  -> (head int32 [P]: the index of the pose's head,
+    mode int32 [P]: 0, 1, ... in order of appearance, n_modes)."""
+    d = np.asarray(matrix, dtype=np.float64)
+    P = d.shape[0]
+    head, mode, heads = np.full(P, -1, dtype=np.int32), np.full(P, -1, dtype=np.int32), []
+    for p in range(P):
+        if np.isnan(d[p, p]):
+            continue
+        near = [m for m, h in enumerate(heads) if d[h, p] <= cutoff]
+        if not near:
+            heads.append(p)
+            near = [len(heads) - 1]
+        head[p], mode[p] = heads[near[0]], near[0]
+    return head, mode, len(heads)
+
+
+def cluster_poses(ligand_pos, mol=None, cutoff=2.0, isomorphisms=None):
+    """Distinct binding modes among the poses of ONE complex, on the host (numpy fp64): `ligand_pos` [P, N, 3] heavy atoms IN RANK ORDER,
+    in the receptor frame (no alignment); `mol` gives the graph isomorphisms (the process-wide cache; None, or an enumeration that raised:
+    the identity mapping), `isomorphisms` = (idx1, idx2) is used as given.  -> (matrix float32 [P, P], head, mode int32 [P], n_modes) with
+    the definitions of pairwise_symmetry_rmsd and modes_from_matrix -- those of cbd_pose_modes, for which this is the reference and the
+    route of an item over its capacity."""
+    lp = np.asarray(ligand_pos, dtype=np.float32)
+    if lp.ndim != 3 or lp.shape[2] != 3:
+        raise ValueError(f"poses {lp.shape}: expected [P, N, 3]")
+    _, entry = _iso_for_item(0, lp.shape[1], mol, isomorphisms)
+    matrix = pairwise_symmetry_rmsd(lp, *entry["iso"])
+    return (matrix,) + modes_from_matrix(matrix, cutoff)
+
+
+def _prepare_cluster_items(items, isomorphisms=None):
+    """Host half of cluster_poses_batch, no GPU: per item (ligand_pos [P, N, 3], mol or None) the fp32 poses, the sizes and the
+    isomorphism cache entry.  -> list of dicts lp, mol, P, N, K, key, entry, fits."""
+    out = []
+    for i, (ligand_pos, mol) in enumerate(items):
+        lp = np.ascontiguousarray(np.asarray(ligand_pos, dtype=np.float32))
+        if lp.ndim != 3 or lp.shape[2] != 3 or lp.shape[1] < 1:
+            raise ValueError(f"item {i}: poses {lp.shape}: expected [P, N, 3]")
+        key, entry = _iso_for_item(i, lp.shape[1], mol, isomorphisms[i] if isomorphisms is not None else None)
+        out.append(dict(lp=lp, mol=mol, P=lp.shape[0], N=lp.shape[1], K=entry["iso"][0].shape[0], key=key, entry=entry,
+                        fits=lp.shape[1] <= MODES_MAX_ATOMS and lp.shape[0] <= MODES_MAX_POSES))
+    return out
+
+
+def _pack_pose_modes(prepared, cutoff=2.0):
+    """The ragged batch cbd_pose_modes reads, as host arrays, for prepared items that fit the kernel; one group per item.  -> dict: grp_n,
+    grp_p, grp_k [G] int32, grp_cutoff [G] float64, pose_ptr, atom_ptr, mat_ptr [G + 1] int32 (prefix sums of P, P * N, P * P), pos
+    float32 [sum P N, 3], idx_ref / idx_pos (lists of the G host tables [K, N]), max_n, max_p."""
+    from .staging import ptr
+    if sum(it["P"] * max(it["P"], it["N"]) for it in prepared) >= 2 ** 31:
+        raise ValueError("cluster_poses_batch: the batch does not fit 32-bit offsets; split it")
+    return dict(
+        grp_n=np.asarray([it["N"] for it in prepared], dtype=np.int32), grp_p=np.asarray([it["P"] for it in prepared], dtype=np.int32),
+        grp_k=np.asarray([it["K"] for it in prepared], dtype=np.int32), grp_cutoff=np.full(len(prepared), cutoff, dtype=np.float64),
+        pose_ptr=ptr([it["P"] for it in prepared]), atom_ptr=ptr([it["P"] * it["N"] for it in prepared]),
+        mat_ptr=ptr([it["P"] * it["P"] for it in prepared]),
+        pos=np.concatenate([it["lp"].reshape(-1, 3) for it in prepared]) if prepared else np.zeros((0, 3), dtype=np.float32),
+        idx_ref=[it["entry"]["iso"][0] for it in prepared], idx_pos=[it["entry"]["iso"][1] for it in prepared],
+        max_n=max((it["N"] for it in prepared), default=0), max_p=max((it["P"] for it in prepared), default=0))
+
+
+def cluster_poses_batch(items, device, cutoff=2.0, isomorphisms=None, return_matrix=False):
+    """cluster_poses for the poses of several complexes at once.  `items`: list of (ligand_pos [P, N, 3] IN RANK ORDER, mol or None), heavy
+    atoms, receptor frame.  -> per item (matrix float32 [P, P] or None, head, mode int32 [P], n_modes).  The isomorphisms come from the
+    process-wide cache and their index tables stay on the device between calls, the same entries and the same LRU as pose_metrics_batch;
+    everything else goes into ONE pinned staging buffer: ONE upload, ONE cbd_pose_modes call on the current stream (the pair kernel and the
+    mode kernel behind it), ONE download, which holds the matrices only with `return_matrix`.  mol None, or a ligand whose enumeration
+    raised: the identity mapping.  An item over the kernel's capacity (N > 512 or P > 256) takes the host route (cluster_poses).
+    `isomorphisms`: optional list with one (idx1, idx2) or None per item, used as given (not cached).  There is no CPU path: `device` must
+    be a GPU."""
+    import ctypes as C
+    from . import engine, staging, molecules_utils as mu
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("cluster_poses_batch groups the poses on the MI355X (cbd_pose_modes); use cluster_poses on the host")
+    lib = engine.load_library()
+    prepared = _prepare_cluster_items(items, isomorphisms)
+    empty = lambda: (np.zeros((0, 0), np.float32) if return_matrix else None, np.zeros(0, np.int32), np.zeros(0, np.int32), 0)
+
+    def host(it):
+        matrix = pairwise_symmetry_rmsd(it["lp"], *it["entry"]["iso"])
+        return (matrix if return_matrix else None,) + modes_from_matrix(matrix, cutoff)
+    results = [None if it["fits"] and it["P"] else (host(it) if it["P"] else empty()) for it in prepared]
+    fit = [it for it, r in zip(prepared, results) if r is None]
+    if not fit:
+        return results
+    pk = _pack_pose_modes(fit, cutoff)
+    G, n_poses, n_atoms, n_matrix = len(fit), int(pk["pose_ptr"][-1]), int(pk["atom_ptr"][-1]), int(pk["mat_ptr"][-1])
+    with torch.cuda.device(dev):
+        tables = [mu._iso_device_tables(it["key"], it["entry"], dev) for it in fit]      # resident; uploaded only when first seen
+        staged, at = staging.upload(dict(
+            {k: pk[k] for k in ("grp_cutoff", "grp_n", "grp_p", "grp_k", "pose_ptr", "atom_ptr", "mat_ptr", "pos")},
+            idx_ref_tab=np.asarray([t[0].data_ptr() for t in tables], dtype=np.uint64),
+            idx_pos_tab=np.asarray([t[1].data_ptr() for t in tables], dtype=np.uint64)), dev)
+        small = 2 * n_poses + G
+        out = torch.empty(small + n_matrix, dtype=torch.int32, device=dev)      # head, mode, n_modes, then the matrices (fp32 bits)
+        part = lambda words: C.c_void_p(out.data_ptr() + 4 * words)
+        engine._check(lib.cbd_pose_modes(
+            G, int(pk["max_n"]), int(pk["max_p"]), n_poses, n_atoms, n_matrix, at("grp_n"), at("grp_p"), at("grp_k"), at("grp_cutoff"),
+            at("pose_ptr"), at("atom_ptr"), at("mat_ptr"), at("pos"), at("idx_ref_tab"), at("idx_pos_tab"), part(small), part(0), part(n_poses),
+            part(2 * n_poses), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        got = (out if return_matrix else out[:small]).cpu().numpy()      # the one download; it also orders `staged` and the tables behind the kernels
+    fit_ids = [i for i, r in enumerate(results) if r is None]
+    for g, (i, it) in enumerate(zip(fit_ids, fit)):
+        p0, p1 = int(pk["pose_ptr"][g]), int(pk["pose_ptr"][g + 1])
+        matrix = None
+        if return_matrix:
+            m0 = small + int(pk["mat_ptr"][g])
+            matrix = got[m0:m0 + it["P"] ** 2].view(np.float32).reshape(it["P"], it["P"]).copy()
+        results[i] = (matrix, got[p0:p1].copy(), got[n_poses + p0:n_poses + p1].copy(), int(got[2 * n_poses + g]))
     return results
 
 

@@ -53,17 +53,55 @@ def _crystal_inputs(orig, predictions_list, ligand_pos):
     return lp, ref, mol
 
 
+def _keep_distinct(candidates, results, positions, confidence_cutoff, cutoff_rmsd, device, group):
+    """args.keep_distinct_rmsd: of each complex's poses above `confidence_cutoff`, only the heads of its binding modes -- the poses are
+    clustered in descending confidence (evaluation.cluster_poses: symmetry-corrected heavy-atom RMSD in the receptor frame, cutoff
+    `cutoff_rmsd`), ONE evaluation.cluster_poses_batch call per `group` consecutive complexes on a GPU `device`, the host route on any
+    other.  `candidates`: [(index into results, predictions_list, final confidences float64 [n]), ...] in the order of `results`.
+    -> [(graph, confidence), ...] in the order the unfiltered list has."""
+    from .evaluation import cluster_poses, cluster_poses_batch
+    on_gpu = torch.device(device).type == "cuda"
+    kept = []
+    for k in range(0, len(candidates), group):
+        chunk, items, picks = candidates[k:k + group], [], []
+        for i, predictions_list, conf in chunk:
+            above = np.flatnonzero(conf > confidence_cutoff)
+            ranked = above[np.argsort(-conf[above], kind="stable")]          # descending confidence, ties in sampling order
+            orig = results[i][0][0]
+            filterHs = torch.not_equal(predictions_list[0]["ligand"].x[:, 0], 0).cpu().numpy()
+            mol = getattr(orig, "mol", None)
+            mol = remove_all_hs(mol[0] if isinstance(mol, (list, tuple)) else mol)
+            picks.append(ranked)
+            items.append((positions[i][ranked][:, filterHs], mol))
+        live = [j for j, ranked in enumerate(picks) if len(ranked)]
+        found = {}
+        if live and on_gpu:
+            found = dict(zip(live, cluster_poses_batch([items[j] for j in live], device, cutoff=cutoff_rmsd)))
+        elif live:
+            found = {j: cluster_poses(*items[j], cutoff=cutoff_rmsd) for j in live}
+        for j, (i, predictions_list, conf) in enumerate(chunk):
+            if j not in found:
+                continue
+            head = found[j][1]
+            heads = set(int(picks[j][r]) for r in range(len(head)) if head[r] == r)
+            kept.extend((predictions_list[i_], float(conf[i_])) for i_ in range(len(predictions_list)) if i_ in heads)
+    return kept
+
+
 def summarize_inference(results, args, filtering_args, confidence_cutoff, device, group=1):
     """The post-processing of inference_epoch (reference finetune_train.py:198-245): `results` = [((orig, data_list, filtering_data_list),
     (predictions_list, confidences)), ...] in sampling order -> (losses, [(graph, confidence), ...] above the cutoff, top-confidence
     RMSDs).  With `args.device_metrics` (opt-in) the RMSDs of each `group` consecutive complexes come from one
     evaluation.pose_metrics_batch call (cached isomorphisms, one upload / launch / download) instead of one get_symmetry_rmsd call per
-    complex and crystal pose; everything else, and the order of every list, is the same."""
+    complex and crystal pose; everything else, and the order of every list, is the same.  With `args.keep_distinct_rmsd` = a cutoff in
+    Angstrom (opt-in, default None) only the heads of each complex's binding modes among the poses above the cutoff are kept
+    (_keep_distinct); `losses` and the top-confidence RMSDs do not change."""
     rmsds, min_rmsds, top_rmsds, confidences_list, complexes_to_keep = [], [], [], [], []
     positions = [np.asarray([g["ligand"].pos.cpu().numpy() for g in predictions_list]) for _, (predictions_list, _) in results]
     inputs = [_crystal_inputs(orig, predictions_list, ligand_pos)
               for ((orig, _, _), (predictions_list, _)), ligand_pos in zip(results, positions)]
     device_rmsd = {}
+    keep_distinct, candidates = getattr(args, "keep_distinct_rmsd", None), []
     if getattr(args, "device_metrics", False):
         from .evaluation import pose_metrics_batch
         for k in range(0, len(results), max(int(group), 1)):
@@ -96,8 +134,13 @@ def summarize_inference(results, args, filtering_args, confidence_cutoff, device
         if confidences is None:
             continue
         confidences_list.extend(float(c) for c in confidences)
+        if keep_distinct is not None:      # opt-in: decided after the loop, one launch per `group` of complexes
+            candidates.append((i, predictions_list, np.asarray([float(c) for c in confidences], dtype=np.float64)))
+            continue
         complexes_to_keep.extend((predictions_list[i_], float(confidences[i_])) for i_ in range(len(predictions_list))
                                  if float(confidences[i_]) > confidence_cutoff)
+    if keep_distinct is not None:
+        complexes_to_keep = _keep_distinct(candidates, results, positions, confidence_cutoff, float(keep_distinct), device, max(int(group), 1))
     rmsds, min_rmsds, top_rmsds, conf = (np.asarray(x, dtype=np.float64) for x in (rmsds, min_rmsds, top_rmsds, confidences_list))
     pct = lambda a, thr, n: float(100 * (a < thr).sum() / n) if n else None
     losses = {"rmsds_lt2": pct(rmsds, 2, len(rmsds)), "rmsds_lt5": pct(rmsds, 5, len(rmsds)),

@@ -318,6 +318,33 @@ int cbd_pose_metrics(int32_t n_poses, int32_t n_complexes, int32_t max_n, int32_
                      const int32_t* const* idx_pos_tab_dev, float* rmsd_out_dev, float* centroid_out_dev, float* min_self_out_dev,
                      int32_t* argmin_ref_out_dev, int32_t* argmin_iso_out_dev, void* stream);
 
+/* Distinct binding modes among sampled poses (no reference counterpart; evaluation.cluster_poses_batch, host restatement
+ * evaluation.cluster_poses), for n_groups groups -- one per complex -- in one call.  Group g has N = grp_n[g] heavy atoms, P = grp_p[g]
+ * poses IN RANK ORDER at pos[atom_ptr[g] ..][P][N][3], K = grp_k[g] graph isomorphisms idx_ref_tab[g] / idx_pos_tab[g] -> [K][N] int32 (as
+ * for cbd_pose_metrics: arrays of n_groups DEVICE pointers in device memory) and a cutoff grp_cutoff[g] in Angstrom (fp64).  pose_ptr,
+ * atom_ptr and mat_ptr [n_groups + 1] are prefix sums of P, P * N and P * P; n_poses, n_atoms and n_matrix are the lengths of head / mode,
+ * of pos (in atoms) and of matrix.  Two kernels behind each other on `stream`:
+ *   matrix [mat_ptr[g] ..][P][P]: for i < j  D[i][j] = float(sqrt(min_k S(i, j, k) / N)), S(i, j, k) = sum_a |x_i[idx_ref[k][a]] -
+ *            x_j[idx_pos[k][a]]|^2 in fp64 on the fp32 coordinates -- cbd_pose_metrics' rmsd with pose i in the place of the crystal pose;
+ *            D[j][i] is written from the same value, the diagonal is 0;
+ *   head / mode [pose_ptr[g] ..][P], n_modes [g]: poses are visited in rank order; pose p joins the best-ranked existing head h with
+ *            D[h][p] <= cutoff (compared in fp64), else it becomes a head.  Only heads are compared against.  head = the index within the
+ *            group of the pose's head, mode = 0, 1, ... in order of appearance, n_modes = the number of heads.
+ * A pose with a coordinate that is not finite gets head = mode = -1 and NaN in its matrix row and column (diagonal included); it is never a
+ * head and does not disturb the others.  Capacity N <= 512, P <= 256 (max_n / max_p: the largest of the launch): larger values return
+ * CBD_ERR_CAPACITY and nothing is launched or written.  A group whose description contradicts itself -- N outside [1, max_n], P outside
+ * [1, max_p], K < 1, prefix extents that differ from P, P * N, P * P, start below 0 or end beyond n_poses / n_atoms / n_matrix, a NULL
+ * index table, or an index outside [0, N) in its tables -- gets head = mode = -1, a NaN matrix and n_modes = -1 (for contradicting sizes
+ * over the extents its prefix entries give, where those lie inside the outputs); the kernels index with none of these before they have
+ * checked it (the lengths of the ragged arrays and of the index tables themselves are the caller's).  No atomics, no scratch memory:
+ * bitwise repeatable, and a group's result does not depend on what shares the launch.  n_groups = 0 returns 0 without a launch.
+ * Device pointers; asynchronous on `stream`. */
+int cbd_pose_modes(int32_t n_groups, int32_t max_n, int32_t max_p, int32_t n_poses, int32_t n_atoms, int32_t n_matrix, const int32_t* grp_n_dev,
+                   const int32_t* grp_p_dev, const int32_t* grp_k_dev, const double* grp_cutoff_dev, const int32_t* pose_ptr_dev,
+                   const int32_t* atom_ptr_dev, const int32_t* mat_ptr_dev, const float* pos_dev, const int32_t* const* idx_ref_tab_dev,
+                   const int32_t* const* idx_pos_tab_dev, float* matrix_out_dev, int32_t* head_out_dev, int32_t* mode_out_dev,
+                   int32_t* n_modes_out_dev, void* stream);
+
 /* Ligand conformers by distance geometry (the first half of the reference's conformer matching: generate_conformer,
  * datasets/process_mols.py:591-607, rdkit's ETKDG there; here plain distance geometry along rdkit's useRandomCoords route, see
  * DESIGN.md section 9 and csrc/conformer_embed.hip).  n_conformers conformers of n_mols molecules in one launch, one workgroup of 4

@@ -4,7 +4,7 @@
                                    | --protein P.pdb[.gz] --ligand-description SMILES|L.sdf|L.mol2
                                    | --protein-ligand-csv FILE)
                        [--samples 10] [--steps 20] [--lm-embeddings E.npy] [--score-model-dir D --ckpt F]
-                       [--confidence-model-dir D --confidence-ckpt F] [--save-visualisation] [--seed 0]
+                       [--confidence-model-dir D --confidence-ckpt F] [--save-visualisation] [--seed 0] [--cluster-rmsd A]
 
 Three ways to name the input:
   --ligand FILE               the conformer is SEEDED FROM THE FILE's coordinates (get_complex): bond lengths and angles of the given
@@ -19,6 +19,10 @@ Three ways to name the input:
 per complex: N shallow copies -> randomize_position -> sampling() with the confidence model -> rank1.sdf,
 rank{k}_confidence{c:.2f}.sdf and, with --save-visualisation, rank{k}_reverseprocess.pdb (the input ligand, the input pose, the
 randomised pose and the pose after every reverse-diffusion step as MODEL frames).
+
+--cluster-rmsd A (default: none) groups the poses of each complex into distinct binding modes: symmetry-corrected heavy-atom RMSD in the
+receptor frame, leader clustering in rank order with cutoff A (docking.ranked_modes: one GPU call per sampling() call), and adds
+mode{m}_rank{k}_confidence{c:.2f}.sdf per mode and modes.csv (mode, head_rank, population, best_confidence, mean_confidence).
 
 A model directory holds model_parameters.yml and the checkpoint.  Without one the model of the shipped architecture is built with
 random weights from --seed: the poses are then meaningless, which is good for a smoke run only.  --lm-embeddings: an .npy of shape
@@ -87,7 +91,7 @@ def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, de
     from confidence_bootstrapping_amd.sampling import sampling, randomize_position
     from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
     from confidence_bootstrapping_amd.visualise import PDBFile
-    from confidence_bootstrapping_amd.docking import write_ranked_poses
+    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes
     remove_hs = bool(getattr(margs, "remove_hs", True))
     with tempfile.TemporaryDirectory() as tmp:
         proteins = [_gunzip(p, tmp, k) for k, p in enumerate(proteins)]
@@ -142,14 +146,20 @@ def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, de
                        filtering_model_args=cargs, batch_size=chunk, no_final_step_noise=a.no_final_step_noise,
                        return_full_trajectory=a.save_visualisation)
         data_list, confidence = out[0], out[1]
+        slices = [slice(g * a.samples, (g + 1) * a.samples) for g in range(len(group))]
+        modes = [None] * len(group)
+        if a.cluster_rmsd is not None:      # the poses of all complexes of this sampling() call in one launch
+            modes = ranked_modes([(cplx.mol, data_list[sl], confidence[sl]) for (_, cplx), sl in zip(group, slices)], dev, a.cluster_rmsd)
         for g, (idx, cplx) in enumerate(group):
-            sl = slice(g * a.samples, (g + 1) * a.samples)
+            sl = slices[g]
             order = write_ranked_poses(out_dirs[idx], cplx.mol, data_list[sl], confidence[sl],
-                                       None if visualization_list is None else visualization_list[sl], remove_hs=remove_hs)
+                                       None if visualization_list is None else visualization_list[sl], remove_hs=remove_hs, modes=modes[g])
             conf = confidence[sl].detach().cpu().numpy().reshape(a.samples, -1)[:, 0]
             print(f"{names[idx]}: {a.samples} poses x {a.steps} steps -> {out_dirs[idx]}")
             for rank, i in enumerate(order[:5]):
                 print(f"  rank {rank + 1}: pose {i:2d}  confidence {conf[i]:+.4f}")
+            if modes[g] is not None:
+                print(f"  {int(modes[g][1].max()) + 1} distinct binding modes at {a.cluster_rmsd} A")
             results.append((names[idx], order, data_list[sl], confidence[sl]))
     return results
 
@@ -173,6 +183,8 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=10)
     ap.add_argument("--no-final-step-noise", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--cluster-rmsd", type=float, default=None, help="group the poses into distinct binding modes with this RMSD cutoff in "
+                    "Angstrom: adds mode*.sdf and modes.csv (default: none)")
     a = ap.parse_args(argv)
     if a.ligand is not None and not a.ligand.endswith((".sdf", ".mol2")):
         ap.error("the ligand must be an .sdf or .mol2 file")
@@ -182,7 +194,7 @@ def main(argv=None):
     from confidence_bootstrapping_amd.sampling import sampling, randomize_position
     from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
     from confidence_bootstrapping_amd.visualise import PDBFile
-    from confidence_bootstrapping_amd.docking import write_ranked_poses
+    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes
     if not torch.cuda.is_available():
         raise RuntimeError("docking runs on the GPU: there is no CPU path")
     dev = torch.device("cuda:0")
@@ -239,11 +251,15 @@ def main(argv=None):
                    filtering_model_args=cargs, batch_size=a.batch_size, no_final_step_noise=a.no_final_step_noise,
                    return_full_trajectory=a.save_visualisation)
     data_list, confidence = out[0], out[1]
-    order = write_ranked_poses(a.out, lig, data_list, confidence, visualization_list, remove_hs=bool(getattr(margs, "remove_hs", True)))
+    modes = None if a.cluster_rmsd is None else ranked_modes([(lig, data_list, confidence)], dev, a.cluster_rmsd)[0]
+    order = write_ranked_poses(a.out, lig, data_list, confidence, visualization_list, remove_hs=bool(getattr(margs, "remove_hs", True)),
+                               modes=modes)
     conf = confidence.detach().cpu().numpy().reshape(len(data_list), -1)[:, 0]
     print(f"{a.samples} poses x {a.steps} steps -> {a.out}")
     for rank, i in enumerate(order[:5]):
         print(f"  rank {rank + 1}: pose {i:2d}  confidence {conf[i]:+.4f}")
+    if modes is not None:
+        print(f"  {int(modes[1].max()) + 1} distinct binding modes at {a.cluster_rmsd} A")
     return order, data_list, confidence
 
 
