@@ -25,6 +25,22 @@ constexpr int NS = 32;
 constexpr int NV = 6;
 constexpr int COL_1O = 32, COL_1E = 50, COL_0O = 68, NODE_DIM = 74;
 
+// ---- shared by the score engine and the all-atom confidence engine (device bodies: graph_build.h) -------------
+// A 2-layer edge MLP whose first layer is split into [constant part | gaussian part | optional 4 bond flags]:
+//   hid = relu(part + WgT^T gauss(d) + WbT^T bond4) ; out = b1 + W1T^T hid     (ns wide: 32 score engine, 24 confidence engine)
+struct EdgeMlp {
+  const float* part;    // [ns] first bias plus the images of the constant inputs: per step (score engine) or folded once (t = 0, confidence)
+  const float* WgT;     // [32 k][ns o]
+  const float* WbT;     // [4][ns o] or nullptr
+  const float* W1T;     // [ns k][ns o]
+  const float* b1;      // [ns]
+  const float* offset;  // [32] gaussian centres (GaussianSmearing.offset)
+  float coeff;          // GaussianSmearing.coeff = -0.5 / (offset[1] - offset[0])^2
+};
+// vec4[e] = unit(pos_dst[dst[e]] - pos_src[src[e]]), dist[e] = |.| of a stored edge list (kernels.hip)
+hipError_t launch_edge_geom(const float* pos_src, const float* pos_dst, const int* src, const int* dst, int n, float* vec4, float* dist,
+                            hipStream_t s);
+
 // ---- tensor-product convolution tiling ----------------------------------------------------------------------
 // One wave (= one workgroup) owns 32 consecutive edges of ONE edge group (the N dimension of v_mfma_f32_32x32x2_f32).
 constexpr int WAVE_EDGES = 32;

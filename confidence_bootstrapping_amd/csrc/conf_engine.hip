@@ -37,13 +37,13 @@ struct EmbedDev {   // AtomEncoder pieces
 
 struct cbd_conf_engine {
   cbd_conf_config cfg{};
-  std::map<std::string, HostTensor> host_w;
+  WeightStore weights;
   bool weights_ready = false, complex_ready = false;
   int* overflow_dev = nullptr;      // sticky capacity-overflow flag (cbd_conf_create / cbd_conf_check)
   DevPool wpool, cpool, bpool;
   // ---- weights
   CLayerDev conv[5];
-  ConfEdgeMlp m_ll{}, m_lr{}, m_la{}, m_rr{}, m_aa{}, m_ar{};
+  EdgeMlp m_ll{}, m_lr{}, m_la{}, m_rr{}, m_aa{}, m_ar{};
   ConfHead atom_head{}, conf_head{};
   EmbedDev emb_lig, emb_rec, emb_atom;
   // ---- complex
@@ -64,24 +64,9 @@ struct cbd_conf_engine {
   bool keep_debug = false;
   std::map<std::string, std::vector<float>> dbg;
   bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-  size_t ev_used = 0;
-  double t_total_ms = 0;
-  int64_t t_n = 0;
+  EventPairPool ev_pool;
+  KernelTimer timer;
 };
-
-static const HostTensor* find_w(cbd_conf_engine* e, const std::string& k) {
-  auto it = e->host_w.find(k);
-  return it == e->host_w.end() ? nullptr : &it->second;
-}
-
-static int need(cbd_conf_engine* e, const std::string& k, std::initializer_list<int64_t> shape, const HostTensor** out) {
-  const HostTensor* t = find_w(e, k);
-  if (!t) return fail(CBD_ERR_WEIGHT, "missing tensor '%s' (load_state_dict strict=True)", k.c_str());
-  if (t->shape != std::vector<int64_t>(shape)) return fail(CBD_ERR_WEIGHT, "tensor '%s' has an unexpected shape", k.c_str());
-  *out = t;
-  return 0;
-}
 
 // ============================================================================================= weight re-packing
 // e3nn FullyConnectedTensorProduct(in, 1x0e+1x1o+1x2e, out, shared_weights=False): instructions in the order
@@ -238,19 +223,19 @@ static int build_conv_layer(cbd_conf_engine* e, int l, int groups, CLayerDev* L)
   for (int g = 0; g < groups; ++g) {
     const std::string fc = prefix + ".fc." + std::to_string(g);
     const HostTensor *w0, *b0, *w1, *b1;
-    CHK(need(e, fc + ".0.weight", {CKDIM, CKDIM}, &w0));
-    CHK(need(e, fc + ".0.bias", {CKDIM}, &b0));
-    CHK(need(e, fc + ".3.weight", {S.weight_numel, CKDIM}, &w1));
-    CHK(need(e, fc + ".3.bias", {S.weight_numel}, &b1));
+    CHK(e->weights.need(fc + ".0.weight", {CKDIM, CKDIM}, &w0));
+    CHK(e->weights.need(fc + ".0.bias", {CKDIM}, &b0));
+    CHK(e->weights.need(fc + ".3.weight", {S.weight_numel, CKDIM}, &w1));
+    CHK(e->weights.need(fc + ".3.bias", {S.weight_numel}, &b1));
     HIPCHK(e->wpool.upload(&L->wstream[g], pack_fctp_stream(IN, OUT, w0->data.data(), b0->data.data(), w1->data.data(), b1->data.data())));
   }
   const int n0o = OUT >= 3 ? CNS : 0, n1e = OUT >= 2 ? CNV : 0;
   const int nf = CNS + CNV + n1e + n0o;
   const HostTensor *bw, *bb, *bm, *bv;
-  CHK(need(e, prefix + ".batch_norm.weight", {nf}, &bw));
-  CHK(need(e, prefix + ".batch_norm.bias", {CNS}, &bb));
-  CHK(need(e, prefix + ".batch_norm.running_mean", {CNS}, &bm));
-  CHK(need(e, prefix + ".batch_norm.running_var", {nf}, &bv));
+  CHK(e->weights.need(prefix + ".batch_norm.weight", {nf}, &bw));
+  CHK(e->weights.need(prefix + ".batch_norm.bias", {CNS}, &bb));
+  CHK(e->weights.need(prefix + ".batch_norm.running_mean", {CNS}, &bm));
+  CHK(e->weights.need(prefix + ".batch_norm.running_var", {nf}, &bv));
   std::vector<float> sc(CN_STRIDE, 0.f), mean(CN_STRIDE, 0.f), bias(CN_STRIDE, 0.f);
   for (int c = 0; c < S.out_dim; ++c) {
     int chn;
@@ -274,14 +259,14 @@ static void sigma_emb_t0(float (&s)[32]) {
 
 // edge embedding MLP `prefix` = Linear(in_dim, 24) ReLU Dropout Linear(24, 24); input layout [bond(4)?][sigma(32)?][gauss(32)]
 static int build_edge_mlp(cbd_conf_engine* e, const std::string& prefix, bool has_bond, bool has_sigma, const std::string& offset_key,
-                          const float* add_out /*[24] or null*/, ConfEdgeMlp* M) {
+                          const float* add_out /*[24] or null*/, EdgeMlp* M) {
   const int in_dim = (has_bond ? 4 : 0) + (has_sigma ? 32 : 0) + 32;
   const HostTensor *w0, *b0, *w1, *b1, *off;
-  CHK(need(e, prefix + ".0.weight", {CNS, in_dim}, &w0));
-  CHK(need(e, prefix + ".0.bias", {CNS}, &b0));
-  CHK(need(e, prefix + ".3.weight", {CNS, CNS}, &w1));
-  CHK(need(e, prefix + ".3.bias", {CNS}, &b1));
-  CHK(need(e, offset_key, {32}, &off));
+  CHK(e->weights.need(prefix + ".0.weight", {CNS, in_dim}, &w0));
+  CHK(e->weights.need(prefix + ".0.bias", {CNS}, &b0));
+  CHK(e->weights.need(prefix + ".3.weight", {CNS, CNS}, &w1));
+  CHK(e->weights.need(prefix + ".3.bias", {CNS}, &b1));
+  CHK(e->weights.need(offset_key, {32}, &off));
   const int sig0 = has_bond ? 4 : 0, g0 = sig0 + (has_sigma ? 32 : 0);
   float sig[32];
   sigma_emb_t0(sig);
@@ -305,7 +290,7 @@ static int build_edge_mlp(cbd_conf_engine* e, const std::string& prefix, bool ha
   HIPCHK(e->wpool.upload(&d_b1, B1));
   HIPCHK(e->wpool.upload(&d_off, off->data));
   const double step = (double)off->data[1] - (double)off->data[0];   // GaussianSmearing.coeff, models/score_model.py:672
-  *M = ConfEdgeMlp{d_WgT, d_WbT, d_W1T, d_b0, d_b1, d_off, (float)(-0.5 / (step * step))};
+  *M = EdgeMlp{d_b0, d_WgT, d_WbT, d_W1T, d_b1, d_off, (float)(-0.5 / (step * step))};
   return 0;
 }
 
@@ -315,7 +300,7 @@ static int build_embed(cbd_conf_engine* e, const std::string& prefix, const std:
   std::vector<int> off;
   for (size_t i = 0; i < dims.size(); ++i) {
     const HostTensor* t;
-    CHK(need(e, prefix + ".atom_embedding_list." + std::to_string(i) + ".weight", {dims[i], CNS}, &t));
+    CHK(e->weights.need(prefix + ".atom_embedding_list." + std::to_string(i) + ".weight", {dims[i], CNS}, &t));
     off.push_back((int)tables.size());
     tables.insert(tables.end(), t->data.begin(), t->data.end());
   }
@@ -326,8 +311,8 @@ static int build_embed(cbd_conf_engine* e, const std::string& prefix, const std:
   if (in_extra_folded + in_extra_live > 0) {
     const int K = CNS + in_extra_folded + in_extra_live;
     const HostTensor *w, *b;
-    CHK(need(e, prefix + ".additional_features_embedder.weight", {CNS, K}, &w));
-    CHK(need(e, prefix + ".additional_features_embedder.bias", {CNS}, &b));
+    CHK(e->weights.need(prefix + ".additional_features_embedder.weight", {CNS, K}, &w));
+    CHK(e->weights.need(prefix + ".additional_features_embedder.bias", {CNS}, &b));
     // layout of the Linear input: [embedding(24) | extra...]; folded (constant) extras come first when present
     std::vector<float> W((size_t)CNS * (CNS + in_extra_live));
     for (int o = 0; o < CNS; ++o) {
@@ -348,18 +333,18 @@ static int build_embed(cbd_conf_engine* e, const std::string& prefix, const std:
 // Linear-BatchNorm1d(eval)-ReLU-Dropout-Linear-BatchNorm1d-ReLU-Dropout-Linear (all_atom_score_model.py:203-226)
 static int build_head(cbd_conf_engine* e, const std::string& prefix, int in_dim, int out_dim, ConfHead* H) {
   const HostTensor *w0, *b0, *w1, *b1, *w2, *b2;
-  CHK(need(e, prefix + ".0.weight", {CNS, in_dim}, &w0));
-  CHK(need(e, prefix + ".0.bias", {CNS}, &b0));
-  CHK(need(e, prefix + ".4.weight", {CNS, CNS}, &w1));
-  CHK(need(e, prefix + ".4.bias", {CNS}, &b1));
-  CHK(need(e, prefix + ".8.weight", {out_dim, CNS}, &w2));
-  CHK(need(e, prefix + ".8.bias", {out_dim}, &b2));
+  CHK(e->weights.need(prefix + ".0.weight", {CNS, in_dim}, &w0));
+  CHK(e->weights.need(prefix + ".0.bias", {CNS}, &b0));
+  CHK(e->weights.need(prefix + ".4.weight", {CNS, CNS}, &w1));
+  CHK(e->weights.need(prefix + ".4.bias", {CNS}, &b1));
+  CHK(e->weights.need(prefix + ".8.weight", {out_dim, CNS}, &w2));
+  CHK(e->weights.need(prefix + ".8.bias", {out_dim}, &b2));
   auto fold = [&](const std::string& bn, const HostTensor* lin_b, std::vector<float>* s, std::vector<float>* t) -> int {
     const HostTensor *g, *bt, *m, *v;
-    CHK(need(e, bn + ".weight", {CNS}, &g));
-    CHK(need(e, bn + ".bias", {CNS}, &bt));
-    CHK(need(e, bn + ".running_mean", {CNS}, &m));
-    CHK(need(e, bn + ".running_var", {CNS}, &v));
+    CHK(e->weights.need(bn + ".weight", {CNS}, &g));
+    CHK(e->weights.need(bn + ".bias", {CNS}, &bt));
+    CHK(e->weights.need(bn + ".running_mean", {CNS}, &m));
+    CHK(e->weights.need(bn + ".running_var", {CNS}, &v));
     s->resize(CNS); t->resize(CNS);
     for (int o = 0; o < CNS; ++o) {
       const float sc = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
@@ -377,20 +362,6 @@ static int build_head(cbd_conf_engine* e, const std::string& prefix, int in_dim,
   HIPCHK(e->wpool.upload(&dW2, w2->data)); HIPCHK(e->wpool.upload(&db2, b2->data));
   *H = ConfHead{dW0, ds0, dt0, dW1, ds1, dt1, dW2, db2, in_dim, out_dim};
   return 0;
-}
-
-// CSR of an edge list by its row 0 (aggregating node), stable in the original column order
-static void csr_by_row0(const int64_t* ei, int E, int n_nodes, std::vector<int>* ptr, std::vector<int>* dst, std::vector<int>* eid) {
-  ptr->assign(n_nodes + 1, 0);
-  for (int k = 0; k < E; ++k) (*ptr)[ei[k] + 1]++;
-  for (int i = 0; i < n_nodes; ++i) (*ptr)[i + 1] += (*ptr)[i];
-  dst->resize(E); eid->resize(E);
-  std::vector<int> fillp(ptr->begin(), ptr->end() - 1);
-  for (int k = 0; k < E; ++k) {
-    const int p = fillp[ei[k]]++;
-    (*dst)[p] = (int)ei[E + k];
-    (*eid)[p] = k;
-  }
 }
 
 // ================================================================================================================ C ABI
@@ -419,7 +390,7 @@ int cbd_conf_destroy(cbd_conf_engine* e) {
   if (!e) return 0;
   (void)hipSetDevice(e->cfg.device);
   (void)hipDeviceSynchronize();
-  for (auto& p : e->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+  e->ev_pool.destroy();
   e->bpool.release(); e->cpool.release(); e->wpool.release();
   if (e->overflow_dev) (void)hipFree(e->overflow_dev);
   delete e;
@@ -428,11 +399,7 @@ int cbd_conf_destroy(cbd_conf_engine* e) {
 
 int cbd_conf_load_weight(cbd_conf_engine* e, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
   if (!e || !name || (!data && ndim > 0)) return fail(CBD_ERR_ARG, "null argument");
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-  t.data.assign(data, data + n);
-  e->host_w[name] = std::move(t);
+  e->weights.load(name, data, shape, ndim);
   e->weights_ready = false;
   return 0;
 }
@@ -449,10 +416,10 @@ int cbd_conf_finalize_weights(cbd_conf_engine* e) {
   float rec_sigma[CNS];
   {
     const HostTensor *w0, *b0, *w1, *b1;
-    CHK(need(e, "rec_sigma_embedding.0.weight", {CNS, 32}, &w0));
-    CHK(need(e, "rec_sigma_embedding.0.bias", {CNS}, &b0));
-    CHK(need(e, "rec_sigma_embedding.3.weight", {CNS, CNS}, &w1));
-    CHK(need(e, "rec_sigma_embedding.3.bias", {CNS}, &b1));
+    CHK(e->weights.need("rec_sigma_embedding.0.weight", {CNS, 32}, &w0));
+    CHK(e->weights.need("rec_sigma_embedding.0.bias", {CNS}, &b0));
+    CHK(e->weights.need("rec_sigma_embedding.3.weight", {CNS, CNS}, &w1));
+    CHK(e->weights.need("rec_sigma_embedding.3.bias", {CNS}, &b1));
     float h[CNS];
     for (int o = 0; o < CNS; ++o) {
       float a = b0->data[o];
@@ -580,7 +547,7 @@ int cbd_conf_set_complex(cbd_conf_engine* e, int32_t Nl, int32_t Nr, int32_t Na,
     HIPCHK(conf_launch_node_embed(d_rx, 1 + lm, 1, e->emb_rec.table_off, e->emb_rec.tables, e->emb_rec.W, lm, e->emb_rec.bias, Nr, e->rec_base, s));
     HIPCHK(conf_launch_node_embed(d_ax, ATOM_N_CAT, ATOM_N_CAT, e->emb_atom.table_off, e->emb_atom.tables, nullptr, 0, e->emb_atom.bias, Na, e->atom_base, s));
   }
-  auto static_edges = [&](const int64_t* ei, int E, const float* pos_src, const float* pos_dst, const ConfEdgeMlp& m, float** attr, float** vec) -> int {
+  auto static_edges = [&](const int64_t* ei, int E, const float* pos_src, const float* pos_dst, const EdgeMlp& m, float** attr, float** vec) -> int {
     std::vector<int> src(E), dst(E);
     for (int k = 0; k < E; ++k) { src[k] = (int)ei[k]; dst[k] = (int)ei[E + k]; }
     int *d_src, *d_dst; float* d_dist;
@@ -588,7 +555,7 @@ int cbd_conf_set_complex(cbd_conf_engine* e, int32_t Nl, int32_t Nr, int32_t Na,
     HIPCHK(cp.alloc(&d_dist, (size_t)E));
     HIPCHK(cp.alloc(vec, (size_t)E * 4));
     HIPCHK(cp.alloc(attr, (size_t)E * CNS));
-    HIPCHK(conf_launch_static_geom(pos_src, pos_dst, d_src, d_dst, E, *vec, d_dist, s));
+    HIPCHK(launch_edge_geom(pos_src, pos_dst, d_src, d_dst, E, *vec, d_dist, s));
     HIPCHK(conf_launch_edge_mlp(m, d_dist, nullptr, nullptr, E, *attr, s));
     return 0;
   };
@@ -759,13 +726,7 @@ static int conf_score_impl(int n, cbd_conf_engine* const* engines, const int32_t
     }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (e0->timing) {      // a merged launch is timed by the first engine
-      if (e0->ev_used == e0->ev_pool.size()) {
-        hipEvent_t x, y;
-        HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
-        e0->ev_pool.emplace_back(x, y);
-      }
-      ev0 = e0->ev_pool[e0->ev_used].first; ev1 = e0->ev_pool[e0->ev_used].second;
-      ++e0->ev_used;
+      HIPCHK(e0->ev_pool.acquire(&ev0, &ev1));
       HIPCHK(hipEventRecord(ev0, s));
     }
     HIPCHK(launch_fctp_conv(L0.in_level, L0.out_level, a, grid, s));
@@ -863,20 +824,13 @@ int cbd_conf_last_edge_counts(cbd_conf_engine* e, int64_t counts[9]) {
 int cbd_conf_kernel_timing(cbd_conf_engine* e, int32_t enable, int32_t reset, double* avg_ms, int64_t* n_launches, double* total_ms) {
   if (!e) return fail(CBD_ERR_ARG, "null engine");
   HIPCHK(hipSetDevice(e->cfg.device));
-  if (e->ev_used > 0) {
+  if (e->ev_pool.used > 0) {
     HIPCHK(hipDeviceSynchronize());
-    for (size_t i = 0; i < e->ev_used; ++i) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, e->ev_pool[i].first, e->ev_pool[i].second));
-      e->t_total_ms += ms;
-      ++e->t_n;
-    }
-    e->ev_used = 0;
+    e->timer.drain(e->ev_pool, 0, e->ev_pool.used);
+    e->ev_pool.used = 0;
   }
-  if (avg_ms) *avg_ms = e->t_n ? e->t_total_ms / (double)e->t_n : 0.0;
-  if (n_launches) *n_launches = e->t_n;
-  if (total_ms) *total_ms = e->t_total_ms;
-  if (reset) { e->t_total_ms = 0; e->t_n = 0; }
+  e->timer.report(avg_ms, n_launches, total_ms);
+  if (reset) e->timer.reset();
   e->timing = enable != 0;
   return 0;
 }

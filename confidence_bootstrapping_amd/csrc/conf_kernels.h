@@ -40,16 +40,6 @@ struct ConfDyn {          // one batch of poses (capacity-sized device buffers)
   int la_cap;             // max ligand->atom edges per ligand atom the buffers were sized for
 };
 
-struct ConfEdgeMlp {      // Linear(gauss[32] (+ bond one-hot[4])) -> ReLU -> Linear, constant inputs folded into b0 / b1
-  const float* WgT;       // [32][24]
-  const float* WbT;       // [4][24] or null
-  const float* W1T;       // [24][24]
-  const float* b0;        // [24]
-  const float* b1;        // [24]
-  const float* offset;    // [32] GaussianSmearing.offset buffer of the checkpoint
-  float coeff;            // GaussianSmearing.coeff = -0.5 / (offset[1] - offset[0])^2
-};
-
 struct ConfHead {         // Linear-BN-ReLU-Linear-BN-ReLU-Linear with eval BatchNorm1d folded into scale/shift
   const float *W0, *s0, *t0;   // [24][in], [24], [24]:  h = relu((W0 x) * s0 + t0)
   const float *W1, *s1, *t1;   // [24][24]
@@ -61,8 +51,7 @@ hipError_t conf_launch_keep(const ConfStatic& cs, const ConfDyn& cd, int B, floa
 hipError_t conf_launch_graph_lig(bool fill, const ConfStatic& cs, const ConfDyn& cd, int B, float lig_r2, int lig_cap, float cross_cut, hipStream_t s);
 hipError_t conf_launch_graph_rec_atom(bool fill, const ConfStatic& cs, const ConfDyn& cd, int B, hipStream_t s);
 hipError_t conf_launch_scan(const ConfDyn& cd, int g0, int g1, const int* n_nodes /*host [9]*/, hipStream_t s);
-hipError_t conf_launch_edge_mlp(const ConfEdgeMlp& m, const float* dist, const float* bond4, const int* count, int cap, float* attr, hipStream_t s);
-hipError_t conf_launch_static_geom(const float* pos_src, const float* pos_dst, const int* src, const int* dst, int n, float* vec, float* dist, hipStream_t s);
+hipError_t conf_launch_edge_mlp(const EdgeMlp& m, const float* dist, const float* bond4, const int* count, int cap, float* attr, hipStream_t s);
 hipError_t conf_launch_node_embed(const float* x, int x_stride, int n_cat, const int* table_off, const float* tables, const float* W,
                                   int in_extra, const float* bias, int n, float* out, hipStream_t s);
 hipError_t conf_launch_node_init(const float* lig_base, const float* rec_base, const float* atom_base, int B, int Nl, int Nr, int Na,

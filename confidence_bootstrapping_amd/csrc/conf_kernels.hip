@@ -1,7 +1,7 @@
 // Graph construction, featurisation and output heads of the all-atom confidence model for gfx950 (MI355X).
 // HBM/latency-bound helpers around fctp_conv.hip; every kernel cites the reference lines it replaces.
 #include "conf_kernels.h"
-#include "device_util.h"
+#include "graph_build.h"
 
 namespace cbd {
 
@@ -18,6 +18,11 @@ __global__ void conf_keep_kernel(ConfStatic cs, ConfDyn cd, int B, float crop2) 
   cd.keep_res[idx] = keep;
 }
 
+struct KeptResidues {   // the crop mask of one pose as the residue predicate of ligand_receptor_edges
+  const int* keep;
+  CBD_DEV bool operator()(int r) const { return keep[r] != 0; }
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // Edges aggregated by LIGAND atoms, one wave per (pose, atom): lig-lig (bonds + radius graph,
 // all_atom_score_model.py:530-553), lig->residue (radius on cutoff-scaled coordinates, :590-597) and lig->atom
@@ -31,77 +36,14 @@ __global__ __launch_bounds__(64) void conf_graph_lig_kernel(ConfStatic cs, ConfD
   const float* P = cd.pos + (size_t)b * cs.Nl * 3;
   const float px = P[3 * a], py = P[3 * a + 1], pz = P[3 * a + 2];
   const int* keep = cd.keep_res + (size_t)b * cs.Nr;
-  // ---- lig-lig
-  {
-    const int nb0 = cs.bond_row[a], nb1 = cs.bond_row[a + 1];
-    int base = 0;
-    if (FILL) {
-      base = cd.start[G_LL][node];
-      for (int k = nb0 + lane; k < nb1; k += 64) {
-        const int e = base + (k - nb0), d = cs.bond_dst[k];
-        float ux, uy, uz, n;
-        unit_vec(P[3 * d] - px, P[3 * d + 1] - py, P[3 * d + 2] - pz, ux, uy, uz, n);
-        cd.src[G_LL][e] = node; cd.dst[G_LL][e] = b * cs.Nl + d; cd.aidx[G_LL][e] = e;
-        reinterpret_cast<f32x4*>(cd.ll_vec)[e] = f32x4{ux, uy, uz, 0.f};
-        cd.ll_dist[e] = n;
-        reinterpret_cast<f32x4*>(cd.ll_bond4)[e] = reinterpret_cast<const f32x4*>(cs.bond_attr)[k];
-      }
-      base += nb1 - nb0;
-    }
-    // radius_graph rows are [neighbour; centre] and the layer aggregates into row 0: atom a receives an edge from every
-    // centre y whose capped scan (first lig_cap+1 in-radius atoms in index order, self included) contains a
-    int kept = 0;
-    for (int c0 = 0; c0 < cs.Nl; c0 += 64) {
-      const int d = c0 + lane;
-      bool ok = false;
-      if (d < cs.Nl && d != a) {
-        const float yx = P[3 * d], yy = P[3 * d + 1], yz = P[3 * d + 2];
-        if (dist2_nofma(px, py, pz, yx, yy, yz) < lig_r2) {
-          int rank = 0;
-          for (int x = 0; x < a; ++x) rank += dist2_nofma(P[3 * x], P[3 * x + 1], P[3 * x + 2], yx, yy, yz) < lig_r2 ? 1 : 0;
-          ok = rank < lig_cap + 1;
-        }
-      }
-      const unsigned long long mk = __ballot(ok);
-      if (FILL && ok) {
-        const int e = base + kept + popc_below(mk, lane);
-        float ux, uy, uz, n;
-        unit_vec(P[3 * d] - px, P[3 * d + 1] - py, P[3 * d + 2] - pz, ux, uy, uz, n);
-        cd.src[G_LL][e] = node; cd.dst[G_LL][e] = b * cs.Nl + d; cd.aidx[G_LL][e] = e;
-        reinterpret_cast<f32x4*>(cd.ll_vec)[e] = f32x4{ux, uy, uz, 0.f};
-        cd.ll_dist[e] = n;
-        reinterpret_cast<f32x4*>(cd.ll_bond4)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      kept += __popcll(mk);
-    }
-    if (!FILL && lane == 0) cd.cnt[G_LL][node] = (nb1 - nb0) + kept;
-  }
-  // ---- lig -> residue
-  {
-    const float lp[3] = {px, py, pz};
-    int n_e = 0;
-    const int base = FILL ? cd.start[G_LR][node] : 0;
-    for (int c0 = 0; c0 < cs.Nr; c0 += 64) {
-      const int r = c0 + lane;
-      bool in = false;
-      if (r < cs.Nr) in = keep[r] != 0 && cross_pair_in(lp, cs.rec_pos + 3 * r, cross_cut);
-      const unsigned long long m = __ballot(in);
-      if (FILL && r < cs.Nr) {
-        int eid = -1;
-        if (in) {
-          eid = base + n_e + popc_below(m, lane);
-          float ux, uy, uz, n;
-          unit_vec(cs.rec_pos[3 * r] - px, cs.rec_pos[3 * r + 1] - py, cs.rec_pos[3 * r + 2] - pz, ux, uy, uz, n);
-          cd.src[G_LR][eid] = node; cd.dst[G_LR][eid] = nL + b * cs.Nr + r; cd.aidx[G_LR][eid] = eid;
-          reinterpret_cast<f32x4*>(cd.lr_vec)[eid] = f32x4{ux, uy, uz, 0.f};
-          cd.lr_dist[eid] = n;
-        }
-        cd.lr_pair[(size_t)node * cs.Nr + r] = eid;
-      }
-      n_e += __popcll(m);
-    }
-    if (!FILL && lane == 0) cd.cnt[G_LR][node] = n_e;
-  }
+  // ---- lig-lig and lig -> residue: the loops of graph_build.h
+  const int n_ll = ligand_ligand_edges<FILL>(P, cs.Nl, a, px, py, pz, node, b * cs.Nl, cs.bond_row, cs.bond_dst, cs.bond_attr, cd.start[G_LL],
+                                             lig_r2, lig_cap, lane,
+                                             EdgeOut{cd.src[G_LL], cd.dst[G_LL], cd.aidx[G_LL], cd.ll_vec, cd.ll_dist, cd.ll_bond4, nullptr});
+  if (!FILL && lane == 0) cd.cnt[G_LL][node] = n_ll;
+  const int n_lr = ligand_receptor_edges<FILL>(px, py, pz, cs.rec_pos, cs.Nr, cross_cut, KeptResidues{keep}, node, nL + b * cs.Nr, cd.start[G_LR],
+                                               lane, EdgeOut{cd.src[G_LR], cd.dst[G_LR], cd.aidx[G_LR], cd.lr_vec, cd.lr_dist, nullptr, cd.lr_pair});
+  if (!FILL && lane == 0) cd.cnt[G_LR][node] = n_lr;
   // ---- lig -> receptor atom
   {
     int n_e = 0;
@@ -253,87 +195,21 @@ __global__ __launch_bounds__(64) void conf_graph_rec_atom_kernel(ConfStatic cs, 
 // exclusive scan of the per-node counts of one edge group per block (blockIdx.x + g0 = group)
 struct ScanArgs { int* cnt[CONF_MAX_GROUPS]; int* start[CONF_MAX_GROUPS]; int n[CONF_MAX_GROUPS]; int* total; int g0; };
 __global__ __launch_bounds__(1024) void conf_scan_kernel(ScanArgs sa) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
   const int g = sa.g0 + blockIdx.x;
-  const int n = sa.n[g];
-  const int* cnt = sa.cnt[g];
-  int* start = sa.start[g];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + tid;
-    const int v = i < n ? cnt[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(x, off, 64);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wsum[w];
-    const int carry = carry_s;
-    if (i < n) start[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) sa.total[g] = carry_s;
+  const int sum = block_exclusive_scan(sa.cnt[g], sa.start[g], sa.n[g]);
+  if (threadIdx.x == 0) sa.total[g] = sum;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Edge embedding MLPs (lig_edge / lr / la / rec_edge / atom_edge / ar_edge _embedding, all_atom_score_model.py:86-96)
 // on GaussianSmearing(dist) (+ bond one-hot): one thread per edge.  The constant sigma-embedding inputs (t = 0) and the
-// constant rec_sigma_emb addend are folded into b0 / b1 by the host.
-struct EdgeMlpArgs { ConfEdgeMlp m; };
-__global__ __launch_bounds__(256) void conf_edge_mlp_kernel(EdgeMlpArgs A, const float* __restrict__ dist, const float* __restrict__ bond4,
+// constant rec_sigma_emb addend are folded into part / b1 by the host; the body is edge_mlp_row of graph_build.h.
+__global__ __launch_bounds__(256) void conf_edge_mlp_kernel(EdgeMlp m, const float* __restrict__ dist, const float* __restrict__ bond4,
                                                             const int* __restrict__ count, int cap, float* __restrict__ attr) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = count ? *count : cap;
   if (e >= n) return;
-  const float d = dist[e];
-  float h[CNS];
-#pragma unroll
-  for (int o = 0; o < CNS; ++o) h[o] = A.m.b0[o];
-  for (int k = 0; k < 32; ++k) {
-    const float t = d - A.m.offset[k];
-    const float gk = expf(A.m.coeff * (t * t));
-#pragma unroll
-    for (int o = 0; o < CNS; ++o) h[o] = fmaf(A.m.WgT[k * CNS + o], gk, h[o]);
-  }
-  if (A.m.WbT) {
-    const f32x4 bb = reinterpret_cast<const f32x4*>(bond4)[e];
-    const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int o = 0; o < CNS; ++o) h[o] = fmaf(A.m.WbT[c * CNS + o], bv[c], h[o]);
-  }
-  float out[CNS];
-#pragma unroll
-  for (int o = 0; o < CNS; ++o) { h[o] = fmaxf(h[o], 0.f); out[o] = A.m.b1[o]; }
-#pragma unroll
-  for (int k = 0; k < CNS; ++k)
-#pragma unroll
-    for (int o = 0; o < CNS; ++o) out[o] = fmaf(A.m.W1T[k * CNS + o], h[k], out[o]);
-  f32x4* dstp = reinterpret_cast<f32x4*>(attr + (size_t)e * CNS);
-#pragma unroll
-  for (int q = 0; q < CNS / 4; ++q) dstp[q] = f32x4{out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]};
-}
-
-// unit vector + length of the stored receptor edges (pose independent; build_rec/atom/cross_rec_conv_graph :556-584,623-633)
-__global__ void conf_static_geom_kernel(const float* __restrict__ pos_src, const float* __restrict__ pos_dst, const int* __restrict__ src,
-                                        const int* __restrict__ dst, int n, float* __restrict__ vec, float* __restrict__ dist) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const int s = src[e], d = dst[e];
-  float ux, uy, uz, nn;
-  unit_vec(pos_dst[3 * d] - pos_src[3 * s], pos_dst[3 * d + 1] - pos_src[3 * s + 1], pos_dst[3 * d + 2] - pos_src[3 * s + 2], ux, uy, uz, nn);
-  reinterpret_cast<f32x4*>(vec)[e] = f32x4{ux, uy, uz, 0.f};
-  dist[e] = nn;
+  edge_mlp_row<CNS>(m, dist, bond4, attr, e);
 }
 
 // AtomEncoder (models/score_model.py:18-41): sum of categorical embeddings, then (optionally) Linear over
@@ -462,18 +338,10 @@ hipError_t conf_launch_scan(const ConfDyn& cd, int g0, int g1, const int* n_node
   return hipGetLastError();
 }
 
-hipError_t conf_launch_edge_mlp(const ConfEdgeMlp& m, const float* dist, const float* bond4, const int* count, int cap, float* attr,
+hipError_t conf_launch_edge_mlp(const EdgeMlp& m, const float* dist, const float* bond4, const int* count, int cap, float* attr,
                                 hipStream_t s) {
   if (cap <= 0) return hipSuccess;
-  EdgeMlpArgs A{m};
-  hipLaunchKernelGGL(conf_edge_mlp_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, A, dist, bond4, count, cap, attr);
-  return hipGetLastError();
-}
-
-hipError_t conf_launch_static_geom(const float* pos_src, const float* pos_dst, const int* src, const int* dst, int n, float* vec,
-                                   float* dist, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(conf_static_geom_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pos_src, pos_dst, src, dst, n, vec, dist);
+  hipLaunchKernelGGL(conf_edge_mlp_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, m, dist, bond4, count, cap, attr);
   return hipGetLastError();
 }
 

@@ -50,7 +50,7 @@ struct MlpDev {   // 2-layer edge MLP pieces
 
 struct cbd_engine {
   cbd_config cfg{};
-  std::map<std::string, HostTensor> host_w;
+  WeightStore weights;
   bool weights_ready = false, complex_ready = false;
   DevPool wpool, cpool, bpool;   // weights / complex / batch workspace
   // "async_setup" = 1: cbd_set_complex works on `setup` (a stream of its own) and waits only for THIS engine's last launches (`ev_last`,
@@ -143,38 +143,21 @@ struct cbd_engine {
 
   // ---- timing of the dominant kernel
   bool timing = false;
-  typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> EvPool;
-  EvPool ev_pool;       // pairs of the eager launches since the last collection
-  size_t ev_used = 0;
-  EvPool gev_pool;      // pairs recorded by the nodes of the cached graphs (GraphEntry::ev_lo/ev_hi index this pool)
-  size_t gev_used = 0;
-  double t_total_ms = 0;
-  int64_t t_n = 0;
+  EventPairPool ev_pool;    // pairs of the eager launches since the last collection
+  EventPairPool gev_pool;   // pairs recorded by the nodes of the cached graphs (GraphEntry::ev_lo/ev_hi index this pool)
+  KernelTimer timer;
 };
 
 static void fill_static_desc(cbd_engine* e);
 static void drop_graphs(cbd_engine* e) {
   for (auto& g : e->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  e->gev_used = 0;   // the event pairs their nodes recorded into are free again
+  e->gev_pool.used = 0;   // the event pairs their nodes recorded into are free again
   e->graphs.clear();
   e->complex_gen = cbd_engine::next_gen();
 }
 
 // ======================================================================================================== weights
-static const HostTensor* find_w(cbd_engine* e, const std::string& k) {
-  auto it = e->host_w.find(k);
-  return it == e->host_w.end() ? nullptr : &it->second;
-}
-
-static int need(cbd_engine* e, const std::string& k, std::initializer_list<int64_t> shape, const HostTensor** out) {
-  const HostTensor* t = find_w(e, k);
-  if (!t) return fail(CBD_ERR_WEIGHT, "missing tensor '%s' (load_state_dict strict=True)", k.c_str());
-  if (t->shape != std::vector<int64_t>(shape)) return fail(CBD_ERR_WEIGHT, "tensor '%s' has an unexpected shape", k.c_str());
-  *out = t;
-  return 0;
-}
-
 // Re-pack one FCBlock (Linear 96->96, ReLU, Linear 96->W) into the tile stream consumed by tp_conv_kernel.
 // See the layout notes at the top of tp_conv.hip.  W2's k order follows the C/D register layout of the first GEMM.
 // Row description of every 32-row weight tile of a layer: which row of W1 / W2 (or none) each MFMA row carries and the
@@ -368,10 +351,10 @@ static int build_conv_layer(cbd_engine* e, const std::string& prefix, int IN, in
   for (int g = 0; g < groups; ++g) {
     const std::string fc = groups == 1 ? prefix + ".fc" : prefix + ".fc." + std::to_string(g);
     const HostTensor *w0, *b0, *w1, *b1;
-    CHK(need(e, fc + ".0.weight", {KDIM, KDIM}, &w0));
-    CHK(need(e, fc + ".0.bias", {KDIM}, &b0));
-    CHK(need(e, fc + ".3.weight", {S.weight_numel, KDIM}, &w1));
-    CHK(need(e, fc + ".3.bias", {S.weight_numel}, &b1));
+    CHK(e->weights.need(fc + ".0.weight", {KDIM, KDIM}, &w0));
+    CHK(e->weights.need(fc + ".0.bias", {KDIM}, &b0));
+    CHK(e->weights.need(fc + ".3.weight", {S.weight_numel, KDIM}, &w1));
+    CHK(e->weights.need(fc + ".3.bias", {S.weight_numel}, &b1));
     std::vector<float> st = pack_conv_stream(IN, OUT, w0->data.data(), b0->data.data(), w1->data.data(), b1->data.data(), true);
     HIPCHK(e->wpool.upload(&L->wstream[g], st));
     HIPCHK(e->wpool.upload(&L->wstream_bf16[g], pack_conv_stream_bf16(IN, OUT, w0->data.data(), b0->data.data(), w1->data.data(), b1->data.data())));
@@ -385,10 +368,10 @@ static int build_conv_layer(cbd_engine* e, const std::string& prefix, int IN, in
   // e3nn BatchNorm (eval) per output column
   const int nf = NS + NV + (OUT >= 2 ? NV : 0) + (OUT >= 3 ? NV : 0);
   const HostTensor *bw, *bb, *bm, *bv;
-  CHK(need(e, prefix + ".batch_norm.weight", {nf}, &bw));
-  CHK(need(e, prefix + ".batch_norm.bias", {NS}, &bb));
-  CHK(need(e, prefix + ".batch_norm.running_mean", {NS}, &bm));
-  CHK(need(e, prefix + ".batch_norm.running_var", {nf}, &bv));
+  CHK(e->weights.need(prefix + ".batch_norm.weight", {nf}, &bw));
+  CHK(e->weights.need(prefix + ".batch_norm.bias", {NS}, &bb));
+  CHK(e->weights.need(prefix + ".batch_norm.running_mean", {NS}, &bm));
+  CHK(e->weights.need(prefix + ".batch_norm.running_var", {nf}, &bv));
   std::vector<float> sc(NODE_STRIDE, 0.f), mean(NODE_STRIDE, 0.f), bias(NODE_STRIDE, 0.f);
   for (int c = 0; c < S.out_dim; ++c) {
     int chn;
@@ -417,11 +400,11 @@ static std::vector<float> transpose_block(const HostTensor* w, int col0, int nco
 static int build_edge_mlp(cbd_engine* e, const std::string& prefix, int in_dim, int gauss_col0, int bond_col0,
                           const std::string& offset_key, MlpDev* M) {
   const HostTensor *w0, *b0, *w1, *b1, *off;
-  CHK(need(e, prefix + ".0.weight", {NS, in_dim}, &w0));
-  CHK(need(e, prefix + ".0.bias", {NS}, &b0));
-  CHK(need(e, prefix + ".3.weight", {NS, NS}, &w1));
-  CHK(need(e, prefix + ".3.bias", {NS}, &b1));
-  CHK(need(e, offset_key, {32}, &off));
+  CHK(e->weights.need(prefix + ".0.weight", {NS, in_dim}, &w0));
+  CHK(e->weights.need(prefix + ".0.bias", {NS}, &b0));
+  CHK(e->weights.need(prefix + ".3.weight", {NS, NS}, &w1));
+  CHK(e->weights.need(prefix + ".3.bias", {NS}, &b1));
+  CHK(e->weights.need(offset_key, {32}, &off));
   HIPCHK(e->wpool.upload(&M->WgT, transpose_block(w0, gauss_col0, 32)));
   if (bond_col0 >= 0) HIPCHK(e->wpool.upload(&M->WbT, transpose_block(w0, bond_col0, 4)));
   HIPCHK(e->wpool.upload(&M->W1T, transpose_block(w1, 0, 32)));
@@ -435,7 +418,7 @@ static int build_edge_mlp(cbd_engine* e, const std::string& prefix, int in_dim, 
 
 static int upload_named(cbd_engine* e, const std::string& k, std::initializer_list<int64_t> shape, const float** dev) {
   const HostTensor* t;
-  CHK(need(e, k, shape, &t));
+  CHK(e->weights.need(k, shape, &t));
   float* p;
   HIPCHK(e->wpool.upload(&p, t->data));
   *dev = p;
@@ -524,8 +507,7 @@ int cbd_destroy(cbd_engine* e) {
   drop_graphs(e);
   if (e->desc_dev) (void)hipFree(e->desc_dev);
   e->wpool.release(); e->cpool.release(); e->bpool.release();
-  for (auto& p : e->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-  for (auto& p : e->gev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+  e->ev_pool.destroy(); e->gev_pool.destroy();
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->side) (void)hipStreamDestroy(e->side);
@@ -542,11 +524,7 @@ int cbd_load_weight(cbd_engine* e, const char* name, const float* data, const in
   const std::string k(name);
   for (const char* pre : {"final_conv.tp.", "tor_bond_conv.tp.", "final_tp_tor."})
     if (k.rfind(pre, 0) == 0) return 0;   // e3nn persistent buffers: arithmetic is hard-wired
-  HostTensor t;
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-  t.data.assign(data, data + n);
-  e->host_w[k] = std::move(t);
+  e->weights.load(k, data, shape, ndim);
   e->weights_ready = false;
   return 0;
 }
@@ -590,10 +568,10 @@ int cbd_finalize_weights(cbd_engine* e) {
   e->lig_emb_tables.clear();
   for (int i = 0; i < 16; ++i) {
     const HostTensor* t;
-    CHK(need(e, "lig_node_embedding.atom_embedding_list." + std::to_string(i) + ".weight", {dims[i], 32}, &t));
+    CHK(e->weights.need("lig_node_embedding.atom_embedding_list." + std::to_string(i) + ".weight", {dims[i], 32}, &t));
     e->lig_emb_tables.push_back(t->data);
   }
-  e->lig_node_w_host = find_w(e, "lig_node_embedding.additional_features_embedder.weight")->data;
+  e->lig_node_w_host = e->weights.find("lig_node_embedding.additional_features_embedder.weight")->data;
   // receptor node encoder
   const float* tmp;
   CHK(upload_named(e, "rec_node_embedding.atom_embedding_list.0.weight", {38, 32}, &tmp));
@@ -614,8 +592,8 @@ int cbd_finalize_weights(cbd_engine* e) {
   CHK(upload_named(e, "final_conv.fc.3.bias", {124}, &ch.fc_b1));
   {
     const HostTensor *bw, *bv;
-    CHK(need(e, "final_conv.batch_norm.weight", {4}, &bw));
-    CHK(need(e, "final_conv.batch_norm.running_var", {4}, &bv));
+    CHK(e->weights.need("final_conv.batch_norm.weight", {4}, &bw));
+    CHK(e->weights.need("final_conv.batch_norm.running_var", {4}, &bv));
     std::vector<float> sc(4);
     for (int c = 0; c < 4; ++c) sc[c] = bw->data[c] * (1.0f / std::sqrt(bv->data[c] + 1e-5f));
     float* p;
@@ -624,9 +602,9 @@ int cbd_finalize_weights(cbd_engine* e) {
     for (int which = 0; which < 2; ++which) {
       const std::string pre = which ? "rot_final_layer" : "tr_final_layer";
       const HostTensor *w0, *w1, *b1;
-      CHK(need(e, pre + ".0.weight", {32, 33}, &w0));
-      CHK(need(e, pre + ".3.weight", {1, 32}, &w1));
-      CHK(need(e, pre + ".3.bias", {1}, &b1));
+      CHK(e->weights.need(pre + ".0.weight", {32, 33}, &w0));
+      CHK(e->weights.need(pre + ".3.weight", {1, 32}, &w1));
+      CHK(e->weights.need(pre + ".3.bias", {1}, &b1));
       std::vector<float> col(32);
       for (int o = 0; o < 32; ++o) col[o] = w0->data[(size_t)o * 33];
       float *pc, *pw, *pb;
@@ -647,15 +625,15 @@ int cbd_finalize_weights(cbd_engine* e) {
     CHK(upload_named(e, "tor_bond_conv.fc.3.bias", {384}, &bh.fc_b1));
     {
       const HostTensor *w0, *b0, *w1, *b1;
-      CHK(need(e, "tor_bond_conv.fc.0.weight", {96, 96}, &w0)); CHK(need(e, "tor_bond_conv.fc.0.bias", {96}, &b0));
-      CHK(need(e, "tor_bond_conv.fc.3.weight", {384, 96}, &w1)); CHK(need(e, "tor_bond_conv.fc.3.bias", {384}, &b1));
+      CHK(e->weights.need("tor_bond_conv.fc.0.weight", {96, 96}, &w0)); CHK(e->weights.need("tor_bond_conv.fc.0.bias", {96}, &b0));
+      CHK(e->weights.need("tor_bond_conv.fc.3.weight", {384, 96}, &w1)); CHK(e->weights.need("tor_bond_conv.fc.3.bias", {384}, &b1));
       HIPCHK(e->wpool.upload(&e->bond_stream, pack_rows_f32(bond_tile_rows(), w0->data.data(), b0->data.data(), w1->data.data(), b1->data.data())));
     }
     const HostTensor *bw, *bb, *bm, *bv;
-    CHK(need(e, "tor_bond_conv.batch_norm.weight", {64}, &bw));
-    CHK(need(e, "tor_bond_conv.batch_norm.bias", {32}, &bb));
-    CHK(need(e, "tor_bond_conv.batch_norm.running_mean", {32}, &bm));
-    CHK(need(e, "tor_bond_conv.batch_norm.running_var", {64}, &bv));
+    CHK(e->weights.need("tor_bond_conv.batch_norm.weight", {64}, &bw));
+    CHK(e->weights.need("tor_bond_conv.batch_norm.bias", {32}, &bb));
+    CHK(e->weights.need("tor_bond_conv.batch_norm.running_mean", {32}, &bm));
+    CHK(e->weights.need("tor_bond_conv.batch_norm.running_var", {64}, &bv));
     // irreps 32x0o + 32x0e: columns 0..31 pseudoscalars (scale only), 32..63 scalars (mean/bias index c-32)
     std::vector<float> sc(64), mean(64, 0.f), bias(64, 0.f);
     for (int c = 0; c < 64; ++c) {
@@ -707,15 +685,7 @@ static int launch_conv_timed(cbd_engine* e, const ConvLayerDev& L, const ConvArg
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     HIPCHK(hipStreamIsCapturing(s, &cs));
     cap = cs == hipStreamCaptureStatusActive;
-    cbd_engine::EvPool& pool = cap ? e->gev_pool : e->ev_pool;
-    size_t& used = cap ? e->gev_used : e->ev_used;
-    if (used == pool.size()) {
-      hipEvent_t a0, a1;
-      HIPCHK(hipEventCreate(&a0)); HIPCHK(hipEventCreate(&a1));
-      pool.push_back({a0, a1});
-    }
-    e0 = pool[used].first; e1 = pool[used].second;
-    ++used;
+    HIPCHK((cap ? e->gev_pool : e->ev_pool).acquire(&e0, &e1));
     CHK(record_event(e0, s, cap));
   }
   if (e->use_bf16 == 1 && e->bf16_stat && L.in_level == 3 && L.out_level == 3 && tp_conv_bf16s_fits(a)) HIPCHK(launch_tp_conv_bf16s(a, e->n_cus, s));
@@ -834,7 +804,7 @@ static int embed_receptor(cbd_engine* e, hipStream_t s) {
   const GraphStatic& gs = e->gs;
   const int Nr = gs.Nr, Err = gs.Err, lm = e->cfg.lm_embedding_dim;
   HIPCHK(launch_rec_node_embed(e->d_rec_x, Nr, lm, e->rec_emb_table, e->rec_node_w, e->rec_node_b, e->X0, s));
-  HIPCHK(launch_edge_geom(gs.rec_pos, e->d_src0, e->d_dst0, Err, e->d_vec0, e->d_dist0, s));
+  HIPCHK(launch_edge_geom(gs.rec_pos, gs.rec_pos, e->d_src0, e->d_dst0, Err, e->d_vec0, e->d_dist0, s));
   {
     EdgeMlpArgs ma{};
     ma.n = 1;
@@ -921,22 +891,14 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
     }
   }
   HIPCHK(e->cpool.upload(&e->lig_static32, lig_static));
-  // bonds sorted by source atom
-  std::vector<int> order(nbd);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bond_index[a] < bond_index[b]; });
-  std::vector<int> bond_row(Nl + 1, 0), bond_dst(nbd);
+  // bonds as a CSR by source atom (stable: the order of a source's bonds is the bond list's)
+  for (int k = 0; k < 2 * nbd; ++k)
+    if (bond_index[k] < 0 || bond_index[k] >= Nl) return fail(CBD_ERR_ARG, "bond index out of range");
+  std::vector<int> bond_row, bond_dst, bond_eid;
+  csr_by_row0(bond_index, nbd, Nl, &bond_row, &bond_dst, &bond_eid);
   std::vector<float> battr((size_t)nbd * 4);
-  int max_bdeg = 0;
-  for (int k = 0; k < nbd; ++k) {
-    const int o = order[k];
-    const int64_t s = bond_index[o], d = bond_index[nbd + o];
-    if (s < 0 || s >= Nl || d < 0 || d >= Nl) return fail(CBD_ERR_ARG, "bond index out of range");
-    bond_row[s + 1]++;
-    bond_dst[k] = (int)d;
-    for (int c = 0; c < 4; ++c) battr[(size_t)k * 4 + c] = bond_attr[(size_t)o * 4 + c];
-  }
-  for (int a = 0; a < Nl; ++a) { max_bdeg = std::max(max_bdeg, bond_row[a + 1]); bond_row[a + 1] += bond_row[a]; }
+  for (int k = 0; k < nbd; ++k)
+    for (int c = 0; c < 4; ++c) battr[(size_t)k * 4 + c] = bond_attr[(size_t)bond_eid[k] * 4 + c];
   std::vector<int> rot_u, rot_v;
   for (int k = 0; k < nbd; ++k)
     if (edge_mask[k]) { rot_u.push_back((int)bond_index[k]); rot_v.push_back((int)bond_index[nbd + k]); }
@@ -958,14 +920,13 @@ int cbd_set_complex(cbd_engine* e, int32_t Nl, int32_t Nr, int32_t nbd, int32_t 
   e->cap_ll_per_sample = nbd + Nl * std::min(Nl - 1, e->cfg.lig_radius_cap + 1);
 
   // ---- receptor statics: kNN edges sorted by aggregating node (row 0)
-  std::vector<int> rorder(Err);
-  std::iota(rorder.begin(), rorder.end(), 0);
-  std::stable_sort(rorder.begin(), rorder.end(), [&](int a, int b) { return rec_edge_index[a] < rec_edge_index[b]; });
-  std::vector<int> src0(Err), dst0(Err), deg0(Nr, 0), ident(Err);
-  for (int k = 0; k < Err; ++k) {
-    const int64_t s = rec_edge_index[rorder[k]], d = rec_edge_index[Err + rorder[k]];
-    if (s < 0 || s >= Nr || d < 0 || d >= Nr) return fail(CBD_ERR_ARG, "receptor edge index out of range");
-    src0[k] = (int)s; dst0[k] = (int)d; deg0[s]++; ident[k] = k;
+  for (int k = 0; k < 2 * Err; ++k)
+    if (rec_edge_index[k] < 0 || rec_edge_index[k] >= Nr) return fail(CBD_ERR_ARG, "receptor edge index out of range");
+  std::vector<int> rr_ptr, dst0, rr_eid, src0(Err), deg0(Nr), ident(Err);
+  csr_by_row0(rec_edge_index, Err, Nr, &rr_ptr, &dst0, &rr_eid);
+  for (int r = 0; r < Nr; ++r) {
+    deg0[r] = rr_ptr[r + 1] - rr_ptr[r];
+    for (int k = rr_ptr[r]; k < rr_ptr[r + 1]; ++k) { src0[k] = r; ident[k] = k; }
   }
   float* d_rec_pos;
   int *d_src0, *d_dst0, *d_deg0, *d_ident;
@@ -1337,23 +1298,13 @@ static int check_batch(cbd_engine* e, int B) {
   return 0;
 }
 
-static void collect_range(cbd_engine* e, const cbd_engine::EvPool& pool, size_t lo, size_t hi) {
-  for (size_t i = lo; i < hi; ++i) {
-    float ms = 0.f;
-    if (hipEventSynchronize(pool[i].second) == hipSuccess && hipEventElapsedTime(&ms, pool[i].first, pool[i].second) == hipSuccess) {
-      e->t_total_ms += ms;
-      e->t_n += 1;
-    }
-  }
-}
-
 // Eager launches: every launch since the last collection has its own event pair.  Captured graphs: the pairs are nodes of the graph
 // and hold the durations of its most recent replay; a graph is read before it is replayed again (sample_impl) and here.
 static void collect_timing(cbd_engine* e) {
-  collect_range(e, e->ev_pool, 0, e->ev_used);
-  e->ev_used = 0;
+  e->timer.drain(e->ev_pool, 0, e->ev_pool.used);
+  e->ev_pool.used = 0;
   for (auto& g : e->graphs)
-    if (g.replayed) { collect_range(e, e->gev_pool, g.ev_lo, g.ev_hi); g.replayed = false; }
+    if (g.replayed) { e->timer.drain(e->gev_pool, g.ev_lo, g.ev_hi); g.replayed = false; }
 }
 
 int cbd_score(cbd_engine* e, int32_t B, const float* pos_dev, const cbd_step* step, float* tr_dev, float* rot_dev, float* tor_dev,
@@ -1478,12 +1429,12 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
   hipGraphExec_t exec = nullptr;
   for (auto& g : e0->graphs)
     if (g.key == key) {
-      if (g.replayed && g.ev_hi > g.ev_lo) { collect_range(e0, e0->gev_pool, g.ev_lo, g.ev_hi); }   // waits for the previous replay
+      if (g.replayed && g.ev_hi > g.ev_lo) { e0->timer.drain(e0->gev_pool, g.ev_lo, g.ev_hi); }   // waits for the previous replay
       exec = g.exec; g.replayed = true;
     }
   if (!exec) {
     hipGraph_t graph = nullptr;
-    const size_t ev_lo = e0->gev_used;
+    const size_t ev_lo = e0->gev_pool.used;
     HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     const int rc = run_steps(nullptr);
     const hipError_t ce = hipStreamEndCapture(s, &graph);
@@ -1496,7 +1447,7 @@ static int sample_impl(int n, cbd_engine* const* E, const int32_t* B, int32_t S,
       (void)hipGraphExecDestroy(e0->graphs.front().exec);
       e0->graphs.erase(e0->graphs.begin());
     }
-    e0->graphs.push_back({key, exec, ev_lo, e0->gev_used, true});
+    e0->graphs.push_back({key, exec, ev_lo, e0->gev_pool.used, true});
   }
   for (int k = 0; k < n; ++k) {
     cbd_engine* e = E[k];
@@ -1779,12 +1730,10 @@ int cbd_last_edge_counts(cbd_engine* e, int64_t counts[5]) {
 int cbd_kernel_timing(cbd_engine* e, int32_t enable, int32_t reset, double* avg_ms, int64_t* n, double* total_ms) {
   if (!e) return fail(CBD_ERR_ARG, "null engine");
   (void)hipSetDevice(e->cfg.device);
-  if (e->ev_used || e->gev_used) { HIPCHK(hipDeviceSynchronize()); collect_timing(e); }
-  if (reset) { e->t_total_ms = 0; e->t_n = 0; }
+  if (e->ev_pool.used || e->gev_pool.used) { HIPCHK(hipDeviceSynchronize()); collect_timing(e); }
+  if (reset) e->timer.reset();
   e->timing = enable != 0;
-  if (avg_ms) *avg_ms = e->t_n ? e->t_total_ms / (double)e->t_n : 0.0;
-  if (n) *n = e->t_n;
-  if (total_ms) *total_ms = e->t_total_ms;
+  e->timer.report(avg_ms, n, total_ms);
   return 0;
 }
 

@@ -32,6 +32,93 @@ struct HostTensor {
   std::vector<float> data;
 };
 
+// The checkpoint tensors an engine was given (cbd_load_weight / cbd_conf_load_weight), by state_dict name
+struct WeightStore {
+  std::map<std::string, HostTensor> w;
+
+  void load(const std::string& name, const float* data, const int64_t* shape, int32_t ndim) {
+    HostTensor t;
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
+    t.data.assign(data, data + n);
+    w[name] = std::move(t);
+  }
+  const HostTensor* find(const std::string& k) const {
+    auto it = w.find(k);
+    return it == w.end() ? nullptr : &it->second;
+  }
+  int need(const std::string& k, std::initializer_list<int64_t> shape, const HostTensor** out) const {
+    const HostTensor* t = find(k);
+    if (!t) return fail(CBD_ERR_WEIGHT, "missing tensor '%s' (load_state_dict strict=True)", k.c_str());
+    if (t->shape != std::vector<int64_t>(shape)) return fail(CBD_ERR_WEIGHT, "tensor '%s' has an unexpected shape", k.c_str());
+    *out = t;
+    return 0;
+  }
+};
+
+// Pairs of HIP events around the launches an engine times, and the running total of what they measured.  acquire() hands out the
+// next pair (the caller records it); drain(lo, hi) reads pairs [lo, hi) into the total -- a pair whose time cannot be read (never
+// recorded, e.g. a captured graph that was not replayed) is skipped.
+struct EventPairPool {
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
+  size_t used = 0;
+
+  hipError_t acquire(hipEvent_t* e0, hipEvent_t* e1) {
+    if (used == pairs.size()) {
+      hipEvent_t a, b;
+      hipError_t r = hipEventCreate(&a);
+      if (r == hipSuccess) r = hipEventCreate(&b);
+      if (r != hipSuccess) return r;
+      pairs.push_back({a, b});
+    }
+    *e0 = pairs[used].first; *e1 = pairs[used].second;
+    ++used;
+    return hipSuccess;
+  }
+  void destroy() {
+    for (auto& p : pairs) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    pairs.clear();
+    used = 0;
+  }
+};
+
+struct KernelTimer {
+  double total_ms = 0;
+  int64_t n = 0;
+
+  void drain(const EventPairPool& pool, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      float ms = 0.f;
+      if (hipEventSynchronize(pool.pairs[i].second) == hipSuccess &&
+          hipEventElapsedTime(&ms, pool.pairs[i].first, pool.pairs[i].second) == hipSuccess) {
+        total_ms += ms;
+        n += 1;
+      }
+    }
+  }
+  void report(double* avg_ms, int64_t* n_launches, double* total) const {
+    if (avg_ms) *avg_ms = n ? total_ms / (double)n : 0.0;
+    if (n_launches) *n_launches = n;
+    if (total) *total = total_ms;
+  }
+  void reset() { total_ms = 0; n = 0; }
+};
+
+// CSR of an edge list [2][E] by its row 0 (the aggregating node), stable in the original column order: ptr [n_nodes + 1], and per
+// slot the row-1 entry (dst) and the original column (eid).  The indices must have been range-checked.
+inline void csr_by_row0(const int64_t* ei, int E, int n_nodes, std::vector<int>* ptr, std::vector<int>* dst, std::vector<int>* eid) {
+  ptr->assign(n_nodes + 1, 0);
+  for (int k = 0; k < E; ++k) (*ptr)[ei[k] + 1]++;
+  for (int i = 0; i < n_nodes; ++i) (*ptr)[i + 1] += (*ptr)[i];
+  dst->resize(E); eid->resize(E);
+  std::vector<int> fillp(ptr->begin(), ptr->end() - 1);
+  for (int k = 0; k < E; ++k) {
+    const int p = fillp[ei[k]]++;
+    (*dst)[p] = (int)ei[E + k];
+    (*eid)[p] = k;
+  }
+}
+
 // Device arena: bump allocation out of large hipMalloc'd chunks.  reset() rewinds without freeing, so the per-complex and
 // per-batch workspaces of successive complexes re-use the same memory (a hipMalloc/hipFree pair per buffer costs more than
 // the kernels of a small complex's set-up); release() returns everything to the runtime.

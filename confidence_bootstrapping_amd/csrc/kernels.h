@@ -4,18 +4,6 @@
 
 namespace cbd {
 
-// A 2-layer edge MLP whose first layer is split into [per-step constant part | gaussian part | optional 4 bond flags]:
-//   hid = relu(part + WgT^T gauss(d) + WbT^T bond4) ; out = b1 + W1T^T hid          (all 32 wide)
-struct EdgeMlp {
-  const float* part;    // [32] per-step constant incl. first bias (or just the bias)
-  const float* WgT;     // [32 k][32 o]
-  const float* WbT;     // [4][32 o] or nullptr
-  const float* W1T;     // [32 k][32 o]
-  const float* b1;      // [32]
-  const float* offset;  // [32] gaussian centres
-  float coeff;
-};
-
 struct GraphStatic {     // per complex, device pointers
   int Nl, Nr, R, nbd, Err;
   int rec_off;                   // joint index of receptor node (b=0, r=0): max_batch * Nl (independent of B)
@@ -126,7 +114,6 @@ hipError_t launch_pose_update(const Multi& m, int step, const SdeCoefs& coefs, i
 
 hipError_t launch_rec_node_embed(const float* rec_x, int Nr, int lm_dim, const float* emb_table, const float* w, const float* b,
                                  float* node, hipStream_t s);
-hipError_t launch_edge_geom(const float* pos, const int* src, const int* dst, int n, float* vec4, float* dist, hipStream_t s);
 hipError_t launch_symm_rmsd(int B, int N, int K, const float* pos, const float* ref, const int* idx_ref, const int* idx_pos, float* out,
                             int* argmin, hipStream_t s);
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t s);

@@ -2,7 +2,7 @@
 // These are the HBM/latency-bound parts of one reverse-diffusion step; the matrix-core work lives in tp_conv.hip.
 // Each kernel cites the reference lines it replaces.  64-wide wavefronts throughout (ballot = 64-bit).
 #include "kernels.h"
-#include "device_util.h"
+#include "graph_build.h"
 #include "pose_math.h"
 
 namespace cbd {
@@ -29,10 +29,15 @@ hipError_t launch_set_desc(const PoseBatch& v, PoseBatch* dst, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ll / lr / rl groups of GraphDyn as the FILL targets of graph_build.h
+CBD_DEV EdgeOut out_ll(const GraphDyn& gd) { return EdgeOut{gd.ll_src, gd.ll_dst, gd.ll_aidx, gd.ll_vec, gd.ll_dist, gd.ll_bond4, nullptr}; }
+CBD_DEV EdgeOut out_lr(const GraphDyn& gd) { return EdgeOut{gd.lr_src, gd.lr_dst, gd.lr_aidx, gd.lr_vec, gd.lr_dist, nullptr, gd.pair_eid}; }
+CBD_DEV EdgeOut out_rl(const GraphDyn& gd) { return EdgeOut{gd.rl_src, gd.rl_dst, gd.rl_aidx, gd.rl_vec, nullptr, nullptr, gd.pair_eid}; }
+
 // ---------------------------------------------------------------------------------------------------------
 // Graph construction.  One wave per node.  Blocks [0, B*Nl) handle ligand nodes (ligand radius graph,
 // score_model.py:502-507, and ligand->receptor cross edges, :564-573); blocks [B*Nl, B*Nl + B*Nr) handle
-// receptor nodes (the flipped cross edges, :356-357).  COUNT pass, single-block scan, FILL pass.
+// receptor nodes (the flipped cross edges, :356-357).  COUNT pass, single-block scan, FILL pass; the loops are graph_build.h's.
 template <bool FILL>
 __global__ __launch_bounds__(64) void graph_kernel(Multi mm, float lig_r2, int lig_cap, float cutoff) {
   int node;
@@ -42,102 +47,23 @@ __global__ __launch_bounds__(64) void graph_kernel(Multi mm, float lig_r2, int l
   const int B = PB.B;
   const int lane = lane_id();
   const int nL = B * gs.Nl;
-  const int roff = gs.rec_off;
   if (node < nL) {
     const int b = node / gs.Nl, a = node % gs.Nl;
     const float* P = gd.pos + (size_t)b * gs.Nl * 3;
     const float px = P[3 * a], py = P[3 * a + 1], pz = P[3 * a + 2];
-    // ---- ligand-ligand: bonds first, then radius-graph edges
-    const int nb0 = gs.bond_row[a], nb1 = gs.bond_row[a + 1];
-    int base = 0;
-    if (FILL) {
-      base = gd.start_ll[node];
-      for (int k = nb0 + lane; k < nb1; k += 64) {
-        const int e = base + (k - nb0), d = gs.bond_dst[k];
-        float ux, uy, uz, n;
-        unit_vec(P[3 * d] - px, P[3 * d + 1] - py, P[3 * d + 2] - pz, ux, uy, uz, n);
-        gd.ll_src[e] = node; gd.ll_dst[e] = b * gs.Nl + d; gd.ll_aidx[e] = e;
-        reinterpret_cast<f32x4*>(gd.ll_vec)[e] = f32x4{ux, uy, uz, 0.f};
-        gd.ll_dist[e] = n;
-        reinterpret_cast<f32x4*>(gd.ll_bond4)[e] = reinterpret_cast<const f32x4*>(gs.bond_attr)[k];
-      }
-      base += nb1 - nb0;
-    }
-    // radius_graph(pos, r, batch) (score_model.py:502) returns [neighbour; centre] rows and the layer aggregates into row 0:
-    // node a receives an edge from every centre y that has a among the first lig_cap+1 in-radius atoms of ITS scan (index
-    // order, self included, torch_cluster radius with max_num_neighbors+1).  rank_y(a) = #{x < a : |x - y| < r}.
-    int kept = 0;
-    for (int c0 = 0; c0 < gs.Nl; c0 += 64) {
-      const int d = c0 + lane;   // candidate centre y
-      bool keep = false;
-      if (d < gs.Nl && d != a) {
-        const float yx = P[3 * d], yy = P[3 * d + 1], yz = P[3 * d + 2];
-        if (dist2_nofma(px, py, pz, yx, yy, yz) < lig_r2) {
-          int rank = 0;
-          for (int x = 0; x < a; ++x) rank += dist2_nofma(P[3 * x], P[3 * x + 1], P[3 * x + 2], yx, yy, yz) < lig_r2 ? 1 : 0;
-          keep = rank < lig_cap + 1;
-        }
-      }
-      const unsigned long long mk = __ballot(keep);
-      if (FILL && keep) {
-        const int e = base + kept + popc_below(mk, lane);
-        float ux, uy, uz, n;
-        unit_vec(P[3 * d] - px, P[3 * d + 1] - py, P[3 * d + 2] - pz, ux, uy, uz, n);
-        gd.ll_src[e] = node; gd.ll_dst[e] = b * gs.Nl + d; gd.ll_aidx[e] = e;
-        reinterpret_cast<f32x4*>(gd.ll_vec)[e] = f32x4{ux, uy, uz, 0.f};
-        gd.ll_dist[e] = n;
-        reinterpret_cast<f32x4*>(gd.ll_bond4)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      kept += __popcll(mk);
-    }
-    if (!FILL && lane == 0) gd.cnt_ll[node] = (nb1 - nb0) + kept;
-    // ---- ligand -> receptor cross edges (cap 10000 never binds for Nr <= 10000)
-    const float lp[3] = {px, py, pz};
-    int nlr = 0;
-    const int lbase = FILL ? gd.start_lr[node] : 0;
-    for (int c0 = 0; c0 < gs.Nr; c0 += 64) {
-      const int r = c0 + lane;
-      bool in = false;
-      if (r < gs.Nr) in = cross_pair_in(lp, gs.rec_pos + 3 * r, cutoff);
-      const unsigned long long m = __ballot(in);
-      if (FILL && r < gs.Nr) {
-        int eid = -1;
-        if (in) {
-          eid = lbase + nlr + popc_below(m, lane);
-          float ux, uy, uz, n;
-          unit_vec(gs.rec_pos[3 * r] - px, gs.rec_pos[3 * r + 1] - py, gs.rec_pos[3 * r + 2] - pz, ux, uy, uz, n);
-          gd.lr_src[eid] = node; gd.lr_dst[eid] = roff + b * gs.Nr + r; gd.lr_aidx[eid] = eid;
-          reinterpret_cast<f32x4*>(gd.lr_vec)[eid] = f32x4{ux, uy, uz, 0.f};
-          gd.lr_dist[eid] = n;
-        }
-        gd.pair_eid[(size_t)node * gs.Nr + r] = eid;
-      }
-      nlr += __popcll(m);
-    }
+    const int nll = ligand_ligand_edges<FILL>(P, gs.Nl, a, px, py, pz, node, b * gs.Nl, gs.bond_row, gs.bond_dst, gs.bond_attr, gd.start_ll,
+                                              lig_r2, lig_cap, lane, out_ll(gd));
+    if (!FILL && lane == 0) gd.cnt_ll[node] = nll;
+    const int nlr = ligand_receptor_edges<FILL>(px, py, pz, gs.rec_pos, gs.Nr, cutoff, AllResidues{}, node, gs.rec_off + b * gs.Nr,
+                                                gd.start_lr, lane, out_lr(gd));
     if (!FILL && lane == 0) gd.cnt_lr[node] = nlr;
-  } else {
-    // ---- receptor node: flipped cross edges (aggregating node = residue, features read from ligand atoms)
+  } else if (!FILL) {
+    // receptor node: count of the flipped cross edges (aggregating node = residue, features read from ligand atoms)
     const int rn = node - nL;
     const int b = rn / gs.Nr, r = rn % gs.Nr;
-    const float* P = gd.pos + (size_t)b * gs.Nl * 3;
-    const float* rp = gs.rec_pos + 3 * r;
-    int nrl = 0;
-    const int rbase = FILL ? gd.start_rl[rn] : 0;
-    for (int c0 = 0; c0 < gs.Nl; c0 += 64) {
-      const int a = c0 + lane;
-      bool in = false;
-      if (a < gs.Nl) in = cross_pair_in(P + 3 * a, rp, cutoff);
-      const unsigned long long m = __ballot(in);
-      if (FILL && in) {
-        const int e = rbase + nrl + popc_below(m, lane);
-        const int lr = gd.pair_eid[(size_t)(b * gs.Nl + a) * gs.Nr + r];
-        const f32x4 vv = reinterpret_cast<const f32x4*>(gd.lr_vec)[lr];
-        gd.rl_src[e] = roff + rn; gd.rl_dst[e] = b * gs.Nl + a; gd.rl_aidx[e] = lr;
-        reinterpret_cast<f32x4*>(gd.rl_vec)[e] = f32x4{-vv.x, -vv.y, -vv.z, 0.f};   // sh(-edge_vec), score_model.py:582
-      }
-      nrl += __popcll(m);
-    }
-    if (!FILL && lane == 0) gd.cnt_rl[rn] = nrl;
+    const int nrl = receptor_ligand_edges<false>(gd.pos + (size_t)b * gs.Nl * 3, gs.Nl, gs.rec_pos, gs.Nr, r, cutoff, 0, 0, 0, nullptr, lane,
+                                                 EdgeOut{});
+    if (lane == 0) gd.cnt_rl[rn] = nrl;
   }
 }
 
@@ -152,27 +78,9 @@ __global__ __launch_bounds__(64) void graph_fill_rec(Multi mm, float cutoff) {
   const PoseBatch& PB = locate(mm, rn);
   const GraphStatic gs = PB.gs;   // by value: kept in scalar registers, not re-read after every store
   const GraphDyn gd = PB.gd;
-  const int lane = lane_id();
-  const int roff = gs.rec_off;
   const int b = rn / gs.Nr, r = rn % gs.Nr;
-  const float* P = gd.pos + (size_t)b * gs.Nl * 3;
-  const float* rp = gs.rec_pos + 3 * r;
-  int nrl = 0;
-  const int rbase = gd.start_rl[rn];
-  for (int c0 = 0; c0 < gs.Nl; c0 += 64) {
-    const int a = c0 + lane;
-    bool in = false;
-    if (a < gs.Nl) in = cross_pair_in(P + 3 * a, rp, cutoff);
-    const unsigned long long m = __ballot(in);
-    if (in) {
-      const int e = rbase + nrl + popc_below(m, lane);
-      const int lr = gd.pair_eid[(size_t)(b * gs.Nl + a) * gs.Nr + r];
-      const f32x4 vv = reinterpret_cast<const f32x4*>(gd.lr_vec)[lr];
-      gd.rl_src[e] = roff + rn; gd.rl_dst[e] = b * gs.Nl + a; gd.rl_aidx[e] = lr;
-      reinterpret_cast<f32x4*>(gd.rl_vec)[e] = f32x4{-vv.x, -vv.y, -vv.z, 0.f};   // sh(-edge_vec), score_model.py:582
-    }
-    nrl += __popcll(m);
-  }
+  receptor_ligand_edges<true>(gd.pos + (size_t)b * gs.Nl * 3, gs.Nl, gs.rec_pos, gs.Nr, r, cutoff, gs.rec_off + rn, b * gs.Nl, gd.start_rl[rn],
+                              gd.lr_vec, lane_id(), out_rl(gd));
 }
 
 // The fill pass runs as two launches: receptor-node blocks read pair_eid / lr_vec written by the ligand-node blocks.
@@ -189,9 +97,6 @@ hipError_t launch_graph_fill(const Multi& m_lig, const Multi& m_rec, float lig_r
 // Exclusive scans of the three per-node count arrays, one 1024-thread workgroup per array (wave-shuffle scan over
 // coalesced 1024-entry chunks), edge totals -> counts[], algorithmic work accounting -> stats[] (bench.py).
 __global__ __launch_bounds__(1024) void graph_scan_kernel(Multi mm) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int which;
   const PoseBatch& PB = locate(mm, which);
   const GraphStatic gs = PB.gs;   // by value: kept in scalar registers, not re-read after every store
@@ -202,29 +107,9 @@ __global__ __launch_bounds__(1024) void graph_scan_kernel(Multi mm) {
   const int* cnt = which == 0 ? gd.cnt_ll : which == 1 ? gd.cnt_lr : gd.cnt_rl;
   int* start = which == 0 ? gd.start_ll : which == 1 ? gd.start_lr : gd.start_rl;
   const int n = which == 2 ? nR : nL;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + tid;
-    const int v = i < n ? cnt[i] : 0;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(x, off, 64);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wsum[w];
-    const int carry = carry_s;
-    if (i < n) start[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const unsigned long long total = (unsigned long long)carry_s;
+  const int sum = block_exclusive_scan(cnt, start, n);
+  if (threadIdx.x == 0) {
+    const unsigned long long total = (unsigned long long)sum;
     gd.counts[which == 0 ? 0 : which == 1 ? 1 : 3] = (int)total;
     if (which == 2) gd.counts[2] = B * gs.Err;
     if (which == 0) gd.counts[4] = 0;   // torsion-edge counter of this forward pass (bond_nb_kernel adds to it later in the stream)
@@ -260,42 +145,10 @@ __global__ __launch_bounds__(256) void edge_mlp_kernel(EdgeMlpArgs a) {
     if (blk >= nb && i + 1 < a.n) { blk -= nb; sg = i + 1; } else break;
   }
   const EdgeSeg& S = a.seg[sg];
-  const EdgeMlp& m = S.m;
-  const float* __restrict__ dist = S.dist;
-  const float* __restrict__ bond4 = S.bond4;
-  float* __restrict__ out = S.out;
   const int n = S.count ? min(*S.count, S.cap) : S.cap;
   const int e = blk * 256 + threadIdx.x;
   if (e >= n) return;
-  const float d = dist[e];
-  float h[32];
-#pragma unroll
-  for (int o = 0; o < 32; ++o) h[o] = m.part[o];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) {
-    const float t = d - m.offset[k];
-    const float gk = expf(m.coeff * (t * t));
-#pragma unroll
-    for (int o = 0; o < 32; ++o) h[o] = fmaf(m.WgT[k * 32 + o], gk, h[o]);
-  }
-  if (m.WbT && bond4) {
-    const f32x4 b = reinterpret_cast<const f32x4*>(bond4)[e];
-    const float bb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int o = 0; o < 32; ++o) h[o] = fmaf(m.WbT[c * 32 + o], bb[c], h[o]);
-  }
-  float r[32];
-#pragma unroll
-  for (int o = 0; o < 32; ++o) { h[o] = fmaxf(h[o], 0.f); r[o] = m.b1[o]; }
-#pragma unroll
-  for (int k = 0; k < 32; ++k)
-#pragma unroll
-    for (int o = 0; o < 32; ++o) r[o] = fmaf(m.W1T[k * 32 + o], h[k], r[o]);
-  f32x4* po = reinterpret_cast<f32x4*>(out + (size_t)e * 32);
-#pragma unroll
-  for (int q = 0; q < 8; ++q) po[q] = f32x4{r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]};
+  edge_mlp_row<32>(S.m, S.dist, S.bond4, S.out, e);
 }
 
 hipError_t launch_edge_mlp(const EdgeMlpArgs& a, hipStream_t s) {
@@ -739,20 +592,22 @@ hipError_t launch_rec_node_embed(const float* rec_x, int Nr, int lm_dim, const f
   return hipGetLastError();
 }
 
-// vec4[e] = unit(pos[dst] - pos[src]), dist[e] = |.|      (receptor kNN edges, score_model.py:531-536)
-__global__ void edge_geom_kernel(const float* __restrict__ pos, const int* __restrict__ src, const int* __restrict__ dst, int n,
-                                 float* __restrict__ vec4, float* __restrict__ dist) {
+// vec4[e] = unit(pos_dst[dst] - pos_src[src]), dist[e] = |.| of a stored edge list: the receptor kNN edges (score_model.py:531-536,
+// pos_src = pos_dst) and the confidence model's residue / atom / atom -> residue graphs (all_atom_score_model.py:556-584,623-633)
+__global__ void edge_geom_kernel(const float* __restrict__ pos_src, const float* __restrict__ pos_dst, const int* __restrict__ src,
+                                 const int* __restrict__ dst, int n, float* __restrict__ vec4, float* __restrict__ dist) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   const int s = src[e], d = dst[e];
   float ux, uy, uz, nn;
-  unit_vec(pos[3 * d] - pos[3 * s], pos[3 * d + 1] - pos[3 * s + 1], pos[3 * d + 2] - pos[3 * s + 2], ux, uy, uz, nn);
+  unit_vec(pos_dst[3 * d] - pos_src[3 * s], pos_dst[3 * d + 1] - pos_src[3 * s + 1], pos_dst[3 * d + 2] - pos_src[3 * s + 2], ux, uy, uz, nn);
   reinterpret_cast<f32x4*>(vec4)[e] = f32x4{ux, uy, uz, 0.f};
   dist[e] = nn;
 }
-hipError_t launch_edge_geom(const float* pos, const int* src, const int* dst, int n, float* vec4, float* dist, hipStream_t s) {
+hipError_t launch_edge_geom(const float* pos_src, const float* pos_dst, const int* src, const int* dst, int n, float* vec4, float* dist,
+                            hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(edge_geom_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pos, src, dst, n, vec4, dist);
+  hipLaunchKernelGGL(edge_geom_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pos_src, pos_dst, src, dst, n, vec4, dist);
   return hipGetLastError();
 }
 

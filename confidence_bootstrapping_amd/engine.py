@@ -217,7 +217,54 @@ def make_steps(t_schedule, model_args, timestep_emb_func, ode=False, no_random=F
     return steps
 
 
-class DockEngine:
+class _EngineBase:
+    """What the two engine classes share: the life of the C handle, weight loading, debug fetches, kernel timing and the current-stream
+    handle.  `_prefix` selects the entry points of include/cbdock.h (cbd_* / cbd_conf_*)."""
+    _prefix = "cbd_"
+
+    def _c(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self._c("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def _loads_key(k):
+        """state_dict entries the engine is given"""
+        return True
+
+    def load_state_dict(self, sd):
+        for k, v in sd.items():
+            if not self._loads_key(k):
+                continue
+            a = np.ascontiguousarray(v.detach().cpu().float().numpy())
+            shape = (C.c_int64 * max(a.ndim, 1))(*a.shape) if a.ndim else (C.c_int64 * 1)(1)
+            _check(self._c("load_weight")(self.h, k.encode(), _hptr(a), shape, a.ndim))
+        _check(self._c("finalize_weights")(self.h))
+        self.complex_key = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def fetch(self, name: str, capacity: int = 1 << 24):
+        buf = np.empty(capacity, dtype=np.float32)
+        n = self._c("debug_fetch")(self.h, name.encode(), _hptr(buf), capacity)
+        if n < 0:
+            raise RuntimeError(self.lib.cbd_last_error().decode())
+        return buf[:n].copy()
+
+    def kernel_timing(self, enable=True, reset=False):
+        avg, n, tot = C.c_double(), C.c_int64(), C.c_double()
+        _check(self._c("kernel_timing")(self.h, int(enable), int(reset), C.byref(avg), C.byref(n), C.byref(tot)))
+        return avg.value, n.value, tot.value
+
+
+class DockEngine(_EngineBase):
     """One engine per (model weights, device).  Holds the C handle; methods mirror the C ABI."""
 
     def __init__(self, device: torch.device, max_batch: int = 64, lm_embedding_dim: int = 1280, no_torsion: bool = False,
@@ -236,23 +283,6 @@ class DockEngine:
         self.max_batch = max_batch
         self.complex_key = None
         self.Nl = self.Nr = self.R = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.cbd_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    # ---- weights
-    def load_state_dict(self, sd):
-        for k, v in sd.items():
-            a = np.ascontiguousarray(v.detach().cpu().float().numpy())
-            shape = (C.c_int64 * max(a.ndim, 1))(*a.shape) if a.ndim else (C.c_int64 * 1)(1)
-            _check(self.lib.cbd_load_weight(self.h, k.encode(), _hptr(a), shape, a.ndim))
-        _check(self.lib.cbd_finalize_weights(self.h))
-        self.complex_key = None
 
     @classmethod
     def from_model(cls, model, device, max_batch: int = 64):
@@ -288,9 +318,6 @@ class DockEngine:
         self.complex_key = key
 
     # ---- compute
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def score(self, pos: torch.Tensor, step: cbd_step):
         B = pos.shape[0]
         pos = pos.to(self.device, torch.float32).contiguous()
@@ -408,22 +435,10 @@ class DockEngine:
     def debug(self, enable=True):
         self.lib.cbd_debug_fetch(self.h, b"enable" if enable else b"disable", None, 0)
 
-    def fetch(self, name: str, capacity: int = 1 << 24):
-        buf = np.empty(capacity, dtype=np.float32)
-        n = self.lib.cbd_debug_fetch(self.h, name.encode(), _hptr(buf), capacity)
-        if n < 0:
-            raise RuntimeError(self.lib.cbd_last_error().decode())
-        return buf[:n].copy()
-
     def edge_counts(self):
         c = (C.c_int64 * 5)()
         _check(self.lib.cbd_last_edge_counts(self.h, c))
         return dict(zip(("ll", "lr", "rr", "rl", "tor"), list(c)))
-
-    def kernel_timing(self, enable=True, reset=False):
-        avg, n, tot = C.c_double(), C.c_int64(), C.c_double()
-        _check(self.lib.cbd_kernel_timing(self.h, int(enable), int(reset), C.byref(avg), C.byref(n), C.byref(tot)))
-        return avg.value, n.value, tot.value
 
 
 class DockEnginePool:
@@ -545,8 +560,9 @@ def pack_fctp_stream(in_level, out_level, w1, b1, w2, b2):
 CONF_GROUPS = ("ll", "lr", "la", "rr", "rl", "ra", "aa", "al", "ar")
 
 
-class ConfidenceEngine:
+class ConfidenceEngine(_EngineBase):
     """All-atom confidence model on one GPU (cbd_conf_* of include/cbdock.h).  One engine per (weights, device)."""
+    _prefix = "cbd_conf_"
 
     def __init__(self, device, max_batch: int = 64, lm_embedding_dim: int = 1280, lig_max_radius=5.0, cross_cutoff=20.0):
         self.lib = load_library()
@@ -562,23 +578,9 @@ class ConfidenceEngine:
         self.complex_key = None
         self.Nl = self.Nr = self.Na = 0
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.cbd_conf_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def load_state_dict(self, sd):
-        for k, v in sd.items():
-            if k.endswith("num_batches_tracked"):
-                continue
-            a = np.ascontiguousarray(v.detach().cpu().float().numpy())
-            shape = (C.c_int64 * max(a.ndim, 1))(*a.shape) if a.ndim else (C.c_int64 * 1)(1)
-            _check(self.lib.cbd_conf_load_weight(self.h, k.encode(), _hptr(a), shape, a.ndim))
-        _check(self.lib.cbd_conf_finalize_weights(self.h))
-        self.complex_key = None
+    @staticmethod
+    def _loads_key(k):
+        return not k.endswith("num_batches_tracked")
 
     @classmethod
     def from_model(cls, model, device, max_batch: int = 64):
@@ -618,8 +620,7 @@ class ConfidenceEngine:
         conf = torch.empty(B, device=self.device)
         atom = torch.empty(B * self.Nl, device=self.device)
         with torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _check(self.lib.cbd_conf_score(self.h, B, _dptr(pos), float(crop_beyond or 0.0), _dptr(conf), _dptr(atom), stream))
+            _check(self.lib.cbd_conf_score(self.h, B, _dptr(pos), float(crop_beyond or 0.0), _dptr(conf), _dptr(atom), self._stream()))
             if check:
                 _check(self.lib.cbd_conf_check(self.h))
         return conf, atom.unsqueeze(1)
@@ -638,8 +639,7 @@ class ConfidenceEngine:
         Bs = (C.c_int32 * n)(*[int(p.shape[0]) for p in poses])
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
         with torch.cuda.device(e0.device):
-            stream = C.c_void_p(torch.cuda.current_stream(e0.device).cuda_stream)
-            _check(e0.lib.cbd_conf_score_multi(n, hs, Bs, arr(poses), float(crop_beyond or 0.0), arr(conf), arr(atom), stream))
+            _check(e0.lib.cbd_conf_score_multi(n, hs, Bs, arr(poses), float(crop_beyond or 0.0), arr(conf), arr(atom), e0._stream()))
             if check:
                 for e in engines:
                     _check(e.lib.cbd_conf_check(e.h))
@@ -653,22 +653,11 @@ class ConfidenceEngine:
     def set_option(self, name: str, value: int):
         _check(self.lib.cbd_conf_set_option(self.h, name.encode(), int(value)))
 
-    def fetch(self, name: str, capacity: int = 1 << 24):
-        buf = np.empty(capacity, dtype=np.float32)
-        n = self.lib.cbd_conf_debug_fetch(self.h, name.encode(), _hptr(buf), capacity)
-        if n < 0:
-            raise RuntimeError(self.lib.cbd_last_error().decode())
-        return buf[:n].copy()
-
     def edge_counts(self):
         c = (C.c_int64 * 9)()
         _check(self.lib.cbd_conf_last_edge_counts(self.h, c))
         return dict(zip(CONF_GROUPS, list(c)))
 
-    def kernel_timing(self, enable=True, reset=False):
-        avg, n, tot = C.c_double(), C.c_int64(), C.c_double()
-        _check(self.lib.cbd_conf_kernel_timing(self.h, int(enable), int(reset), C.byref(avg), C.byref(n), C.byref(tot)))
-        return avg.value, n.value, tot.value
 
 
 def _single_all_atom_complex(data):

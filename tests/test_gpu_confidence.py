@@ -120,6 +120,39 @@ def test_confidence_edge_cases(conf_model):
     eng.set_complex(cplx)
 
 
+@pytest.mark.parametrize("Nl,Nr", [(64, 64), (65, 65), (70, 48)])
+def test_graph_builder_at_the_wavefront_and_cap_edges(conf_model, score_model, Nl, Nr):
+    """The ligand graph loops the two engines share (csrc/graph_build.h), from the confidence engine's side: exactly one wavefront
+    of candidate centres, one atom past it, and the size of the score engine's cap test (test_gpu_edge_cases.py).  Pose 0 is the
+    ligand plus 0.1 A noise; pose 1 has every atom inside a ball, so the neighbour cap (32) binds; the crop drops residues."""
+    from confidence_bootstrapping_amd.engine import DockEngine, make_steps
+    from confidence_bootstrapping_amd.synthetic import add_atoms, make_complex
+    model, _ = conf_model
+    smodel, sargs = score_model
+    cplx = add_atoms(make_complex(Nl=Nl, Nr=Nr, R=3, knn=8, seed=11), seed=11)
+    g = torch.Generator().manual_seed(2)
+    pos = cplx["ligand"].pos[None].repeat(2, 1, 1) + 0.1 * torch.randn(2, Nl, 3, generator=g)
+    pos[1] = cplx["ligand"].pos.mean(0) + 1.1 * torch.randn(Nl, 3, generator=g).clamp(-1.5, 1.5)
+    ref = _oracle(model, cplx, pos, crop=20.0)
+    eng = model.engine()
+    eng.set_complex(cplx)
+    eng.set_option("debug", 1)
+    conf, atom = eng.score(pos.cuda(), crop_beyond=20.0)
+    eng.set_option("debug", 0)
+    counts = eng.edge_counts()
+    want = dict(zip(("ll", "lr", "la", "rr", "rl", "ra", "aa", "al", "ar"), ref["edge_counts"].tolist()))
+    assert counts == want, (counts, want)
+    _check_layers(eng, ref, 2 * Nl)
+    assert (conf.cpu() - ref["confidence"]).abs().max() < 2e-5
+    assert (atom.cpu() - ref["atom_confidence"]).abs().max() < 2e-5
+    # the score engine builds the same ligand graph (radius 5 A, cap 32) from the same loop
+    dock = DockEngine(torch.device("cuda:0"), max_batch=2)
+    dock.load_state_dict(smodel.state_dict())
+    dock.set_complex(cplx)
+    dock.score(pos.cuda(), make_steps(np.array([0.7]), sargs, smodel.timestep_emb_func)[0])
+    assert dock.edge_counts()["ll"] == counts["ll"]
+
+
 def test_confidence_forward_api(conf_model):
     """forward(batch) with the reference's contract: Batch of poses of one complex -> (confidence [B], atom_confidence [B*Nl,1])."""
     from confidence_bootstrapping_amd import Batch
