@@ -111,3 +111,59 @@ def ranked_modes(groups, device, cutoff=2.0):
         mode[order] = mode_r
         out.append((head, mode))
     return out
+
+
+POSE_CHECK_COLUMNS = ("rank", "confidence", "valid", "n_bad_bond", "n_bad_angle", "n_internal_clash", "n_rec_clash", "bond_lo", "bond_hi",
+                      "angle_lo", "angle_hi", "clash_ratio", "rec_ratio", "rec_dist", "rec_lig_atom", "rec_atom", "flags")
+
+
+def pose_check_rows(groups, device, **thresholds):
+    """Are the docked poses physically possible?  `groups` = [(mol, data_list, confidence or None, receptor graph or None), ...]: the first
+    three as write_ranked_poses takes them, the fourth a graph with an 'atom' store (the complex that was docked; its protein heavy atoms
+    are the receptor) or None (internal checks only).  The heavy-atom poses of each complex are put in rank order (write_ranked_poses'
+    ranking) and checked in absolute coordinates with evaluation.pose_checks' four distance checks: ONE evaluation.pose_checks_batch call
+    for all groups on a GPU `device`, evaluation.pose_checks per group on any other.  -> [(order, conf float64 [n] or None, PoseChecks whose
+    arrays are IN RANK ORDER), ...]: write_pose_checks' `rows`."""
+    from .evaluation import ligand_check_tables, pose_checks, pose_checks_batch, receptor_check_atoms
+    from .molecules_utils import _graph_of
+    cpu = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    items, ranked, receptors = [], [], {}
+    for mol, data_list, confidence, graph in groups:
+        pos = np.stack([cpu(g["ligand"].pos).astype(np.float32) + cpu(g.original_center).astype(np.float32).reshape(1, 3) for g in data_list])
+        conf, order = _ranking(confidence, len(data_list), cpu)
+        tables = None
+        if mol is not None:
+            nums = _graph_of(mol)[0]
+            tables = ligand_check_tables(mol)
+            if pos.shape[1] == len(nums) and (nums == 1).any():      # the graphs carry the hydrogens: the checks are on heavy atoms
+                pos = pos[:, nums != 1]
+            if len(tables[3]) != pos.shape[1]:
+                tables = None
+        if graph is not None and id(graph) not in receptors:      # complexes docked into the same graph object share one receptor upload
+            rec = receptor_check_atoms(graph)
+            receptors[id(graph)] = None if rec is None else (rec[0] + cpu(graph.original_center).astype(np.float32).reshape(1, 3), rec[1])
+        items.append((pos[order], tables, receptors.get(id(graph)) if graph is not None else None))
+        ranked.append((np.asarray(order), conf))
+    if torch.device(device).type == "cuda":
+        found = pose_checks_batch(items, device, **thresholds)
+    else:
+        found = [pose_checks(*item, **thresholds) for item in items]
+    return [(order, conf, checks) for (order, conf), checks in zip(ranked, found)]
+
+
+def write_pose_checks(out_dir, rows):
+    """`rows` = one entry of pose_check_rows -> `out_dir`/pose_checks.csv, one row per rank (POSE_CHECK_COLUMNS): rank, confidence (empty
+    without confidences), valid (1 / 0), the four counts, the seven ratios and distances (bond_lo .. rec_dist; nan where a check did not
+    run), the closest receptor atom as (rec_lig_atom, rec_atom) and the flags of evaluation.pose_checks.  Returns the path."""
+    order, conf, checks = rows
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "pose_checks.csv")
+    with open(path, "w") as f:
+        f.write(",".join(POSE_CHECK_COLUMNS) + "\n")
+        for rank, idx in enumerate(order):
+            cells = [str(rank + 1), "" if conf is None else f"{conf[idx]:.6f}", str(int(checks.valid[rank]))]
+            for name in POSE_CHECK_COLUMNS[3:]:
+                v = getattr(checks, name)[rank]
+                cells.append(f"{float(v):.6f}" if v.dtype == np.float32 else str(int(v)))
+            f.write(",".join(cells) + "\n")
+    return path

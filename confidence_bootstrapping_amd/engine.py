@@ -76,6 +76,7 @@ SYMBOLS = {
     "cbd_randomize_poses": (C.c_int, [C.c_int32] * 5 + [_P] * 16),
     "cbd_pose_metrics": (C.c_int, [C.c_int32] * 4 + [_P] * 16),
     "cbd_pose_modes": (C.c_int, [C.c_int32] * 6 + [_P] * 15),
+    "cbd_pose_checks": (C.c_int, [C.c_int32] * 4 + [_P] * 12 + [C.c_float] * 4 + [_P] * 2),
     "cbd_embed_conformers": (C.c_int, [C.c_int32] * 4 + [_P] * 13 + [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [_P] * 4),
     "cbd_conf_create": (C.c_int, [C.POINTER(cbd_conf_config), C.POINTER(_P)]),
     "cbd_conf_destroy": (C.c_int, [_P]),

@@ -7,6 +7,8 @@ entries index with the DESCENDING confidence order, inference.py:782-785, 812-81
 Table-driven instead of the reference's 290 unrolled lines.
 `cluster_poses` / `cluster_poses_batch` (no reference counterpart): the distinct binding modes among the poses of a complex, on the host
 and on the GPU (`cbd_pose_modes`).
+`pose_checks` / `pose_checks_batch` (no reference counterpart): is a pose physically possible -- bond lengths, 1-3 distances, internal and
+receptor clashes, on the host and on the GPU (`cbd_pose_checks`).
 """
 from __future__ import annotations
 
@@ -292,6 +294,323 @@ def cluster_poses_batch(items, device, cutoff=2.0, isomorphisms=None, return_mat
             m0 = small + int(pk["mat_ptr"][g])
             matrix = got[m0:m0 + it["P"] ** 2].view(np.float32).reshape(it["P"], it["P"]).copy()
         results[i] = (matrix, got[p0:p1].copy(), got[n_poses + p0:n_poses + p1].copy(), int(got[2 * n_poses + g]))
+    return results
+
+
+CHECKS_MAX_ATOMS = 256      # capacity of cbd_pose_checks per ligand (include/cbdock.h)
+CHECK_BAD_BOND, CHECK_BAD_ANGLE, CHECK_INTERNAL_CLASH, CHECK_REC_CLASH = 1, 2, 4, 8
+CHECK_NO_TABLES, CHECK_NO_RECEPTOR, CHECK_BAD_COORD, CHECK_BAD_TABLE = 16, 32, 64, 128
+CHECK_FAILED = CHECK_BAD_BOND | CHECK_BAD_ANGLE | CHECK_INTERNAL_CLASH | CHECK_REC_CLASH | CHECK_BAD_COORD | CHECK_BAD_TABLE
+CHECK_THRESHOLDS = dict(bond_tol=0.25, angle_tol=0.25, clash_tol=0.30, rec_scale=0.75)      # the PoseBusters choices: DESIGN.md section 9
+DEFAULT_RADIUS = 2.0          # Angstrom, for an element conformer_embedding._VDW does not list
+CHECK_FLOATS = ("bond_lo", "bond_hi", "angle_lo", "angle_hi", "clash_ratio", "rec_ratio", "rec_dist")      # the rows of cbd_pose_checks' output, in order
+CHECK_INTS = ("n_bad_bond", "n_bad_angle", "n_internal_clash", "n_rec_clash", "rec_lig_atom", "rec_atom", "flags")
+PoseChecks = __import__("collections").namedtuple("PoseChecks", ("valid",) + CHECK_FLOATS + CHECK_INTS)
+PoseChecks.__doc__ = """[P] arrays per pose: valid (bool: no check that ran failed), seven float32 and seven int32 (evaluation.pose_checks)"""
+
+
+def _check_thresholds(thresholds):
+    """the four thresholds as the kernel holds them: fp32 -> (bond_tol, angle_tol, clash_tol, rec_scale) as np.float32"""
+    unknown = set(thresholds) - set(CHECK_THRESHOLDS)
+    if unknown:
+        raise TypeError(f"unknown threshold(s) {sorted(unknown)}: expected {sorted(CHECK_THRESHOLDS)}")
+    t = {k: np.float32(thresholds.get(k, v)) for k, v in CHECK_THRESHOLDS.items()}
+    if not all(0 <= t[k] < 1 for k in ("bond_tol", "angle_tol", "clash_tol")) or not (t["rec_scale"] > 0 and np.isfinite(t["rec_scale"])):
+        raise ValueError(f"thresholds {t}: the three tolerances lie in [0, 1), rec_scale is positive")
+    return t["bond_tol"], t["angle_tol"], t["clash_tol"], t["rec_scale"]
+
+
+def _checks_from_rows(floats, ints):
+    """float32 [7, P] and int32 [7, P] in the order of CHECK_FLOATS / CHECK_INTS -> PoseChecks"""
+    return PoseChecks((ints[6] & CHECK_FAILED) == 0, *(np.ascontiguousarray(r) for r in floats), *(np.ascontiguousarray(r) for r in ints))
+
+
+def pose_checks(ligand_pos, tables=None, receptor=None, **thresholds):
+    """Is a pose physically possible?  Four distance checks in the style of PoseBusters on the poses of ONE complex, on the host (numpy
+    fp64): the definition of cbd_pose_checks and the route of a ligand over its capacity.
+    `ligand_pos` [P, N, 3] heavy atoms (fp32); `tables` = (lower, upper, kind, lig_radius) from ligand_check_tables -- lower / upper fp32
+    [N, N], kind uint8 [N, N] (1 a bond, 2 a 1-3 pair, 0 any other pair; symmetric, only i < j is read), lig_radius fp32 [N]; the first
+    three may be None (no internal checks), the whole may be None (then every ligand atom gets carbon's radius, 1.7 A); `receptor` =
+    (rec_pos [A, 3], rec_radius [A]) in the frame of the poses, or None.  Thresholds (held as fp32): bond_tol = angle_tol = 0.25,
+    clash_tol = 0.30, rec_scale = 0.75.
+    Distances are sqrt(dx*dx + dy*dy + dz*dz) in fp64 on the fp32 coordinates; sums of radii and threshold products fp64 on the fp32 values;
+    every float is rounded to fp32 once.  Per pose over the pairs i < j:
+      kind 1: n_bad_bond counts d < (1 - bond_tol) lower or d > (1 + bond_tol) upper; bond_lo = min d / lower, bond_hi = max d / upper;
+      kind 2: n_bad_angle, angle_lo, angle_hi, the same with angle_tol;
+      kind 0: n_internal_clash counts d < (1 - clash_tol) lower; clash_ratio = min d / lower;
+    and over all N x A pairs, ratio = d / (r_i + r_a): n_rec_clash counts ratio < rec_scale; rec_ratio = min ratio at (rec_lig_atom,
+    rec_atom), ties to the smaller ligand atom, then the smaller receptor atom; rec_dist = min d (not necessarily the same pair).
+    A category without pairs: count 0, +inf for a minimum, -inf for a maximum.
+    flags: 1 bad bond, 2 bad angle, 4 internal clash, 8 receptor clash, 16 internal checks not evaluated (no tables), 32 receptor checks
+    not evaluated (no receptor, or one without atoms), 64 a coordinate of the pose or of the receptor that is not finite, 128 a malformed
+    table entry among i < j (not finite, lower <= 0, upper < lower, kind > 2) or, where the receptor checks run, a radius that is not
+    finite and positive.  With 64 or 128 every float is NaN, every count and both atoms -1 and bits 1 to 8 are clear; with 16 the internal
+    fields are NaN / -1, with 32 the receptor fields.  valid = none of 1, 2, 4, 8, 64, 128: a pose passes on the checks that ran.
+    -> PoseChecks of [P] arrays."""
+    bond_tol, angle_tol, clash_tol, rec_scale = (float(t) for t in _check_thresholds(thresholds))
+    lp = np.asarray(ligand_pos, dtype=np.float32)
+    if lp.ndim != 3 or lp.shape[2] != 3 or lp.shape[1] < 1:
+        raise ValueError(f"poses {lp.shape}: expected [P, N, 3]")
+    P, N = lp.shape[:2]
+    lower, upper, kind, radius = tables if tables is not None else (None, None, None, None)
+    radius = np.full(N, 1.7, dtype=np.float32) if radius is None else np.asarray(radius, dtype=np.float32)
+    if radius.shape != (N,):
+        raise ValueError(f"{radius.shape} ligand radii for {N} atoms")
+    has_tab = lower is not None
+    has_rec = receptor is not None and len(receptor[0]) > 0
+    x = lp.astype(np.float64)
+    floats, ints = np.full((7, P), np.nan, dtype=np.float32), np.full((7, P), -1, dtype=np.int32)
+    flags = np.full(P, (0 if has_tab else CHECK_NO_TABLES) | (0 if has_rec else CHECK_NO_RECEPTOR), dtype=np.int32)
+    flags[~np.isfinite(lp).all(axis=(1, 2))] |= CHECK_BAD_COORD
+    if has_tab:
+        lower, upper, kind = np.asarray(lower, dtype=np.float32), np.asarray(upper, dtype=np.float32), np.asarray(kind)
+        if lower.shape != (N, N) or upper.shape != (N, N) or kind.shape != (N, N):
+            raise ValueError(f"tables {lower.shape} / {upper.shape} / {kind.shape} for {N} atoms")
+        i, j = np.triu_indices(N, 1)
+        lo, up, kd = lower[i, j].astype(np.float64), upper[i, j].astype(np.float64), kind[i, j].astype(np.int64)
+        with np.errstate(invalid="ignore"):
+            if not (np.isfinite(lo) & np.isfinite(up) & (lo > 0) & (up >= lo) & (kd >= 0) & (kd <= 2)).all():
+                flags |= CHECK_BAD_TABLE
+    if has_rec:
+        rec_pos, rec_radius = np.asarray(receptor[0], dtype=np.float32), np.asarray(receptor[1], dtype=np.float32)
+        if rec_pos.ndim != 2 or rec_pos.shape[1] != 3 or rec_radius.shape != rec_pos.shape[:1]:
+            raise ValueError(f"receptor {rec_pos.shape} / {rec_radius.shape}: expected [A, 3] and [A]")
+        if not np.isfinite(rec_pos).all():
+            flags |= CHECK_BAD_COORD
+        if not all((np.isfinite(r) & (r > 0)).all() for r in (radius, rec_radius)):
+            flags |= CHECK_BAD_TABLE
+        y, radius_sum = rec_pos.astype(np.float64), radius.astype(np.float64)[:, None] + rec_radius.astype(np.float64)[None]
+    for p in np.flatnonzero((flags & (CHECK_BAD_COORD | CHECK_BAD_TABLE)) == 0):
+        if has_tab:
+            dx, dy, dz = (x[p, i, a] - x[p, j, a] for a in range(3))
+            d = np.sqrt(dx * dx + dy * dy + dz * dz)
+            for k, (tol, n_row, lo_row, hi_row, bit) in enumerate(((clash_tol, 2, 4, None, CHECK_INTERNAL_CLASH), (bond_tol, 0, 0, 1, CHECK_BAD_BOND),
+                                                                   (angle_tol, 1, 2, 3, CHECK_BAD_ANGLE))):
+                m = kd == k
+                bad = d[m] < (1.0 - tol) * lo[m]
+                if hi_row is not None:
+                    bad |= d[m] > (1.0 + tol) * up[m]
+                    floats[hi_row, p] = (d[m] / up[m]).max(initial=-np.inf)
+                floats[lo_row, p] = (d[m] / lo[m]).min(initial=np.inf)
+                ints[n_row, p] = bad.sum()
+                flags[p] |= bit if bad.any() else 0
+        if has_rec:
+            dx, dy, dz = (x[p, :, None, a] - y[None, :, a] for a in range(3))
+            d = np.sqrt(dx * dx + dy * dy + dz * dz)
+            ratio = d / radius_sum
+            best = int(np.argmin(ratio))          # the first minimum in (ligand atom, receptor atom) order
+            floats[5, p], floats[6, p] = ratio.flat[best], d.min()
+            ints[3, p], ints[4, p], ints[5, p] = (ratio < rec_scale).sum(), best // ratio.shape[1], best % ratio.shape[1]
+            flags[p] |= CHECK_REC_CLASH if ints[3, p] else 0
+    ints[6] = flags
+    return _checks_from_rows(floats, ints)
+
+
+_CHECK_TABLES = __import__("collections").OrderedDict()      # key -> (lower, upper, kind, lig_radius)
+_CHECK_TABLES_CFG = {"limit": 256}
+_CHECK_TABLES_COUNT = {"hits": 0, "misses": 0}
+
+
+def check_tables_cache_clear():
+    _CHECK_TABLES.clear()
+    _CHECK_TABLES_COUNT.update(hits=0, misses=0)
+
+
+def check_tables_cache_stats():
+    return {"entries": len(_CHECK_TABLES), **_CHECK_TABLES_COUNT}
+
+
+def ligand_check_tables(mol, ref_pos=None):
+    """What pose_checks needs of a ligand: (lower, upper fp32 [N, N], kind uint8 [N, N], lig_radius fp32 [N]) for its HEAVY atoms in their
+    order (a molecule that carries hydrogens is stripped on a copy; the poses must be filtered likewise).  lower / upper: the
+    triangle-smoothed matrices of conformer_embedding.distance_bounds(mol, ref_pos if given else mol.pos) -- the pose only settles which side
+    of a double bond and which hand of a centre the 1-4 bounds describe; kind from the bond graph: topological distance 1 -> 1, 2 -> 2,
+    3 and more (or another fragment) -> 0; lig_radius: conformer_embedding._VDW, DEFAULT_RADIUS = 2.0 A for an element it does not list.  The
+    molecule is perceived (on a copy) if it is not.  When distance_bounds refuses the ligand -- more than 256 atoms, an element outside its
+    bond-length table, an object that is only a graph (atomicnums / adjacency_matrix) -- the three tables are None and the radii are still
+    returned.  Cached per ligand in a small LRU keyed on the graph as the isomorphism cache is (molecules_utils.isomorphism_key), plus bond
+    orders, charges and the pose; check_tables_cache_clear() empties it."""
+    import copy
+    import hashlib
+    from . import molecules_utils as mu
+    from .datasets import conformer_embedding as ce, molfile
+    nums, adjacency = mu._graph_of(mol)
+    is_mol = isinstance(mol, molfile.Mol)
+    if ref_pos is None and is_mol and len(mol.pos) == len(nums):
+        ref_pos = mol.pos
+    heavy = np.asarray(nums) != 1
+    ref = None if ref_pos is None else np.ascontiguousarray(np.asarray(ref_pos, dtype=np.float64))
+    if ref is not None and len(ref) == len(heavy):
+        ref = np.ascontiguousarray(ref[heavy])
+    h = hashlib.blake2b(digest_size=20)
+    h.update(mu.isomorphism_key(nums, adjacency).encode())
+    if is_mol:
+        h.update(np.asarray([(b.a, b.b, b.type) for b in mol.bonds], dtype=np.int64).tobytes())
+        h.update(np.asarray([a.charge for a in mol.atoms], dtype=np.int64).tobytes())
+        h.update(b"-" if ref is None else ref.tobytes())
+    key = h.hexdigest()
+    hit = _CHECK_TABLES.get(key)
+    if hit is not None:
+        _CHECK_TABLES.move_to_end(key)
+        _CHECK_TABLES_COUNT["hits"] += 1
+        return hit
+    _CHECK_TABLES_COUNT["misses"] += 1
+    radius = np.asarray([ce._VDW.get(int(z), DEFAULT_RADIUS) for z in np.asarray(nums)[heavy]], dtype=np.float32)
+    lower = upper = kind = None
+    if is_mol:
+        try:
+            work = copy.deepcopy(mol)
+            if not heavy.all():
+                work = molfile.remove_hs(work)
+            if not work.perceived:
+                molfile.perceive(work)
+            if work.GetNumAtoms() != len(radius):
+                raise ValueError("hydrogens that RemoveHs keeps")
+            lo64, up64, _ = ce.distance_bounds(work, ref if ref is not None and ref.shape == (len(radius), 3) else None)
+            n = len(radius)
+            am = np.asarray(work.adjacency_matrix) != 0
+            two = (am.astype(np.int64) @ am.astype(np.int64)) > 0
+            kind = np.where(am, 1, np.where(two, 2, 0)).astype(np.uint8)
+            kind[np.arange(n), np.arange(n)] = 0
+            lower, upper = lo64.astype(np.float32), up64.astype(np.float32)
+        except (ValueError, KeyError) as e:
+            print("pose checks: no internal checks for this ligand:", e)
+            lower = upper = kind = None
+    out = (lower, upper, kind, radius)
+    _CHECK_TABLES[key] = out
+    while len(_CHECK_TABLES) > _CHECK_TABLES_CFG["limit"]:
+        _CHECK_TABLES.popitem(last=False)
+    return out
+
+
+def receptor_check_atoms(graph):
+    """(rec_pos fp32 [A, 3], rec_radius fp32 [A]) of a complex's all-atom graph: graph['atom'].pos (the graph's frame: centred on
+    original_center) and conformer_embedding._VDW of the atomic number behind graph['atom'].x[:, 1]
+    (process_mols.allowable_features['possible_atomic_num_list']); the 'misc' entry and an element _VDW does not list get DEFAULT_RADIUS =
+    2.0 A.  None when the graph has no 'atom' store.  Protein heavy atoms only: the graph holds neither hydrogens nor waters nor cofactors."""
+    from .datasets import conformer_embedding as ce
+    from .datasets.process_mols import allowable_features
+    if graph is None or "atom" not in graph or getattr(graph["atom"], "pos", None) is None:
+        return None
+    cpu = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    store = graph["atom"]
+    table = np.asarray([ce._VDW.get(z, DEFAULT_RADIUS) if isinstance(z, int) else DEFAULT_RADIUS
+                        for z in allowable_features["possible_atomic_num_list"]], dtype=np.float32)
+    index = np.clip(cpu(store.x)[:, 1].astype(np.int64), 0, len(table) - 1)
+    return np.ascontiguousarray(cpu(store.pos), dtype=np.float32).reshape(-1, 3), table[index]
+
+
+def _prepare_check_items(items):
+    """Host half of pose_checks_batch, no GPU: per item (ligand_pos [P, N, 3], mol or (lower, upper, kind, lig_radius) or None, (rec_pos,
+    rec_radius) or None) the fp32 arrays and sizes.  -> list of dicts lp, P, N, tables (the 4-tuple pose_checks takes), receptor (fp32
+    pair or None), rec_key (the identity of the item's rec_pos object, None without atoms), fits."""
+    out = []
+    for k, (ligand_pos, ligand, receptor) in enumerate(items):
+        lp = np.ascontiguousarray(np.asarray(ligand_pos, dtype=np.float32))
+        if lp.ndim != 3 or lp.shape[2] != 3 or lp.shape[1] < 1:
+            raise ValueError(f"item {k}: poses {lp.shape}: expected [P, N, 3]")
+        n = lp.shape[1]
+        if ligand is None:
+            tables = (None, None, None, np.full(n, 1.7, dtype=np.float32))
+        elif isinstance(ligand, (tuple, list)):
+            tables = tuple(ligand)
+        else:
+            tables = ligand_check_tables(ligand)
+        lower, upper, kind, radius = tables
+        radius = np.ascontiguousarray(np.asarray(radius, dtype=np.float32))
+        if radius.shape != (n,):
+            raise ValueError(f"item {k}: {radius.shape} ligand radii for {n} atoms")
+        if lower is not None:
+            lower, upper, kind = np.asarray(lower, dtype=np.float32), np.asarray(upper, dtype=np.float32), np.asarray(kind).astype(np.uint8)
+            if lower.shape != (n, n) or upper.shape != (n, n) or kind.shape != (n, n):
+                raise ValueError(f"item {k}: tables {lower.shape} / {upper.shape} / {kind.shape} for {n} atoms")
+        rec, rec_key = None, None
+        if receptor is not None and len(receptor[0]) > 0:
+            rec = (np.ascontiguousarray(np.asarray(receptor[0], dtype=np.float32)), np.ascontiguousarray(np.asarray(receptor[1], dtype=np.float32)))
+            if rec[0].ndim != 2 or rec[0].shape[1] != 3 or rec[1].shape != rec[0].shape[:1]:
+                raise ValueError(f"item {k}: receptor {rec[0].shape} / {rec[1].shape}: expected [A, 3] and [A]")
+            rec_key = id(receptor[0])
+        out.append(dict(lp=lp, P=lp.shape[0], N=n, tables=(lower, upper, kind, radius), receptor=rec, rec_key=rec_key, fits=n <= CHECKS_MAX_ATOMS))
+    return out
+
+
+def _pack_pose_checks(prepared):
+    """The ragged batch cbd_pose_checks reads, as host arrays, for prepared items that fit the kernel; one complex per item, its poses in
+    order; items with the same rec_key share one receptor.  -> dict: pose_cplx [P], pose_ptr [P + 1] (atoms), pos fp32 [sum N, 3],
+    lig_radius fp32 [sum N] (one per atom of pos), cplx_n, cplx_rec (-1: none), cplx_tab (0 / 1) [C], tab_ptr [C + 1] (entries: N * N
+    rounded up to a multiple of four for a complex with tables, else 0), bounds fp32 (per complex [N][N]: upper at i < j, lower at j < i, the
+    diagonal 0) and kind uint8 of tab_ptr[-1] entries each, kind_words = kind viewed as int32 (what the staging buffer takes), rec_ptr
+    [R + 1] (atoms), rec fp32 [sum A, 4] = (x, y, z, radius), max_n, n_receptors."""
+    from .staging import ptr
+    rec_ids, recs, cplx_rec = {}, [], []
+    for it in prepared:
+        if it["rec_key"] is None:
+            cplx_rec.append(-1)
+            continue
+        if it["rec_key"] not in rec_ids:
+            rec_ids[it["rec_key"]] = len(recs)
+            recs.append(np.concatenate([it["receptor"][0], it["receptor"][1][:, None]], axis=1))
+        cplx_rec.append(rec_ids[it["rec_key"]])
+    sizes = [((it["N"] ** 2 + 3) & ~3) if it["tables"][0] is not None else 0 for it in prepared]
+    if sum(sizes) >= 2 ** 31 or sum(it["P"] * it["N"] for it in prepared) >= 2 ** 31 or sum(len(r) for r in recs) >= 2 ** 31:
+        raise ValueError("pose_checks_batch: the batch does not fit 32-bit offsets; split it")
+    tab_ptr = ptr(sizes)
+    bounds, kind = np.zeros(int(tab_ptr[-1]), dtype=np.float32), np.zeros(int(tab_ptr[-1]), dtype=np.uint8)
+    for t0, it in zip(tab_ptr[:-1], prepared):
+        lower, upper, kd, _ = it["tables"]
+        if lower is not None:
+            n = it["N"]
+            bounds[t0:t0 + n * n] = (np.triu(upper, 1) + np.tril(lower, -1)).reshape(-1)
+            kind[t0:t0 + n * n] = kd.reshape(-1)
+    return dict(
+        pose_cplx=np.asarray([c for c, it in enumerate(prepared) for _ in range(it["P"])], dtype=np.int32),
+        pose_ptr=ptr([it["N"] for it in prepared for _ in range(it["P"])]),
+        pos=np.concatenate([it["lp"].reshape(-1, 3) for it in prepared]) if prepared else np.zeros((0, 3), dtype=np.float32),
+        lig_radius=np.concatenate([np.tile(it["tables"][3], it["P"]) for it in prepared]) if prepared else np.zeros(0, dtype=np.float32),
+        cplx_n=np.asarray([it["N"] for it in prepared], dtype=np.int32), cplx_rec=np.asarray(cplx_rec, dtype=np.int32),
+        cplx_tab=np.asarray([int(s > 0) for s in sizes], dtype=np.int32), tab_ptr=tab_ptr, bounds=bounds, kind=kind, kind_words=kind.view(np.int32),
+        rec_ptr=ptr([len(r) for r in recs]), rec=np.concatenate(recs) if recs else np.zeros((0, 4), dtype=np.float32),
+        max_n=max((it["N"] for it in prepared), default=0), n_receptors=len(recs))
+
+
+def pose_checks_batch(items, device, **thresholds):
+    """pose_checks for the poses of several complexes at once.  `items`: list of (ligand_pos [P, N, 3] heavy atoms, mol or (lower, upper,
+    kind, lig_radius) or None, (rec_pos [A, 3], rec_radius [A]) in the frame of the poses or None) -> per item a PoseChecks of [P] arrays.  A
+    mol goes through ligand_check_tables (cached); None: no internal checks and carbon's radius for every atom.  Items that hold the SAME
+    rec_pos array object share one receptor entry: a screening run of many ligands against one receptor uploads it once.  Everything goes
+    into ONE pinned staging buffer: ONE upload, ONE cbd_pose_checks launch on the current stream, ONE download.  An item with N > 256 takes
+    the host route (pose_checks).  Thresholds as pose_checks.  There is no CPU path: `device` must be a GPU."""
+    import ctypes as C
+    from . import engine, staging
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pose_checks_batch checks the poses on the MI355X (cbd_pose_checks); use pose_checks on the host")
+    tols = _check_thresholds(thresholds)
+    lib = engine.load_library()
+    prepared = _prepare_check_items(items)
+    empty = lambda: _checks_from_rows(np.zeros((7, 0), np.float32), np.zeros((7, 0), np.int32))
+    results = [None if it["fits"] and it["P"] else (pose_checks(it["lp"], it["tables"], it["receptor"], **thresholds) if it["P"] else empty())
+               for it in prepared]
+    fit = [it for it, r in zip(prepared, results) if r is None]
+    if not fit:
+        return results
+    pk = _pack_pose_checks(fit)
+    n_poses = len(pk["pose_cplx"])
+    with torch.cuda.device(dev):
+        # rec first: with no 8-byte part in front of it, it starts at the buffer's base, aligned for the kernel's 16-byte loads
+        staged, at = staging.upload({k: pk[k] for k in ("rec", "pose_cplx", "pose_ptr", "pos", "lig_radius", "cplx_n", "cplx_rec", "cplx_tab",
+                                                        "tab_ptr", "bounds", "kind_words", "rec_ptr")}, dev)
+        out = torch.empty(14, n_poses, dtype=torch.int32, device=dev)
+        engine._check(lib.cbd_pose_checks(
+            n_poses, len(fit), int(pk["n_receptors"]), int(pk["max_n"]), at("pose_cplx"), at("pose_ptr"), at("pos"), at("lig_radius"), at("cplx_n"),
+            at("cplx_rec"), at("cplx_tab"), at("tab_ptr"), at("bounds"), at("kind_words"), at("rec_ptr"), at("rec"), *(C.c_float(float(t)) for t in tols),
+            C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        got = out.cpu().numpy()      # the one download; it also orders `staged` behind the kernel
+    p0 = 0
+    for i in [i for i, r in enumerate(results) if r is None]:
+        p1 = p0 + prepared[i]["P"]
+        results[i] = _checks_from_rows(got[:7, p0:p1].view(np.float32), got[7:, p0:p1])
+        p0 = p1
     return results
 
 

@@ -53,11 +53,46 @@ def _crystal_inputs(orig, predictions_list, ligand_pos):
     return lp, ref, mol
 
 
-def _keep_distinct(candidates, results, positions, confidence_cutoff, cutoff_rmsd, device, group):
+def _valid_poses(results, positions, device, group):
+    """args.keep_valid: per complex a bool [n] -- evaluation.pose_checks' `valid` of each sampled pose (bond lengths, 1-3 distances,
+    internal and receptor clashes on heavy atoms).  The receptor atoms come from the complex's all-atom graph: the first graph of
+    `filtering_data_list` when it has an 'atom' store, else `orig`, shifted into the frame of the poses if the two `original_center`s
+    differ; without an 'atom' store only the internal checks run.  ONE evaluation.pose_checks_batch call per `group` consecutive complexes
+    on a GPU `device`, the host route on any other."""
+    from .evaluation import ligand_check_tables, pose_checks, pose_checks_batch, receptor_check_atoms
+    on_gpu = torch.device(device).type == "cuda"
+    cpu = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    valid = []
+    for k in range(0, len(results), group):
+        items = []
+        for ((orig, _, filtering_data_list), (predictions_list, _)), ligand_pos in zip(results[k:k + group], positions[k:k + group]):
+            filterHs = torch.not_equal(predictions_list[0]["ligand"].x[:, 0], 0).cpu().numpy()
+            mol = getattr(orig, "mol", None)
+            mol = mol[0] if isinstance(mol, (list, tuple)) else mol
+            tables = None if mol is None else ligand_check_tables(mol)
+            if tables is not None and len(tables[3]) != int(filterHs.sum()):
+                print("pose checks: the molecule does not match the poses; no internal checks for this complex")
+                tables = None
+            receptor = None
+            for graph in ([filtering_data_list[0]] if filtering_data_list else []) + [orig]:
+                receptor = receptor_check_atoms(graph)
+                if receptor is not None:
+                    shift = (cpu(graph.original_center).reshape(1, 3) - cpu(orig.original_center).reshape(1, 3)).astype(np.float32)
+                    if np.any(shift != 0):
+                        receptor = (receptor[0] + shift, receptor[1])
+                    break
+            items.append((ligand_pos[:, filterHs], tables, receptor))
+        found = pose_checks_batch(items, device) if on_gpu else [pose_checks(*item) for item in items]
+        valid.extend(np.asarray(f.valid, dtype=bool) for f in found)
+    return valid
+
+
+def _keep_distinct(candidates, results, positions, confidence_cutoff, cutoff_rmsd, device, group, valid=None):
     """args.keep_distinct_rmsd: of each complex's poses above `confidence_cutoff`, only the heads of its binding modes -- the poses are
     clustered in descending confidence (evaluation.cluster_poses: symmetry-corrected heavy-atom RMSD in the receptor frame, cutoff
     `cutoff_rmsd`), ONE evaluation.cluster_poses_batch call per `group` consecutive complexes on a GPU `device`, the host route on any
     other.  `candidates`: [(index into results, predictions_list, final confidences float64 [n]), ...] in the order of `results`.
+    `valid`: the per-complex masks of _valid_poses (args.keep_valid), or None: only valid poses are clustered.
     -> [(graph, confidence), ...] in the order the unfiltered list has."""
     from .evaluation import cluster_poses, cluster_poses_batch
     on_gpu = torch.device(device).type == "cuda"
@@ -65,7 +100,7 @@ def _keep_distinct(candidates, results, positions, confidence_cutoff, cutoff_rms
     for k in range(0, len(candidates), group):
         chunk, items, picks = candidates[k:k + group], [], []
         for i, predictions_list, conf in chunk:
-            above = np.flatnonzero(conf > confidence_cutoff)
+            above = np.flatnonzero(conf > confidence_cutoff if valid is None else (conf > confidence_cutoff) & valid[i])
             ranked = above[np.argsort(-conf[above], kind="stable")]          # descending confidence, ties in sampling order
             orig = results[i][0][0]
             filterHs = torch.not_equal(predictions_list[0]["ligand"].x[:, 0], 0).cpu().numpy()
@@ -95,13 +130,17 @@ def summarize_inference(results, args, filtering_args, confidence_cutoff, device
     evaluation.pose_metrics_batch call (cached isomorphisms, one upload / launch / download) instead of one get_symmetry_rmsd call per
     complex and crystal pose; everything else, and the order of every list, is the same.  With `args.keep_distinct_rmsd` = a cutoff in
     Angstrom (opt-in, default None) only the heads of each complex's binding modes among the poses above the cutoff are kept
-    (_keep_distinct); `losses` and the top-confidence RMSDs do not change."""
+    (_keep_distinct); `losses` and the top-confidence RMSDs do not change.  With `args.keep_valid` (opt-in, default absent / False) a pose is
+    kept only if evaluation.pose_checks calls it valid (_valid_poses: one pose_checks_batch call per `group` on a GPU device); validity is
+    decided first, so with `keep_distinct_rmsd` the modes are formed among the valid poses; `losses` and the top-confidence RMSDs do not
+    change either."""
     rmsds, min_rmsds, top_rmsds, confidences_list, complexes_to_keep = [], [], [], [], []
     positions = [np.asarray([g["ligand"].pos.cpu().numpy() for g in predictions_list]) for _, (predictions_list, _) in results]
     inputs = [_crystal_inputs(orig, predictions_list, ligand_pos)
               for ((orig, _, _), (predictions_list, _)), ligand_pos in zip(results, positions)]
     device_rmsd = {}
     keep_distinct, candidates = getattr(args, "keep_distinct_rmsd", None), []
+    valid = _valid_poses(results, positions, device, max(int(group), 1)) if getattr(args, "keep_valid", False) else None
     if getattr(args, "device_metrics", False):
         from .evaluation import pose_metrics_batch
         for k in range(0, len(results), max(int(group), 1)):
@@ -138,9 +177,10 @@ def summarize_inference(results, args, filtering_args, confidence_cutoff, device
             candidates.append((i, predictions_list, np.asarray([float(c) for c in confidences], dtype=np.float64)))
             continue
         complexes_to_keep.extend((predictions_list[i_], float(confidences[i_])) for i_ in range(len(predictions_list))
-                                 if float(confidences[i_]) > confidence_cutoff)
+                                 if float(confidences[i_]) > confidence_cutoff and (valid is None or valid[i][i_]))
     if keep_distinct is not None:
-        complexes_to_keep = _keep_distinct(candidates, results, positions, confidence_cutoff, float(keep_distinct), device, max(int(group), 1))
+        complexes_to_keep = _keep_distinct(candidates, results, positions, confidence_cutoff, float(keep_distinct), device, max(int(group), 1),
+                                           valid=valid)
     rmsds, min_rmsds, top_rmsds, conf = (np.asarray(x, dtype=np.float64) for x in (rmsds, min_rmsds, top_rmsds, confidences_list))
     pct = lambda a, thr, n: float(100 * (a < thr).sum() / n) if n else None
     losses = {"rmsds_lt2": pct(rmsds, 2, len(rmsds)), "rmsds_lt5": pct(rmsds, 5, len(rmsds)),

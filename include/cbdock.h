@@ -345,6 +345,41 @@ int cbd_pose_modes(int32_t n_groups, int32_t max_n, int32_t max_p, int32_t n_pos
                    const int32_t* const* idx_pos_tab_dev, float* matrix_out_dev, int32_t* head_out_dev, int32_t* mode_out_dev,
                    int32_t* n_modes_out_dev, void* stream);
 
+/* Is a pose physically possible?  Four PoseBusters-style distance checks (no reference counterpart: inference.py:398 declares
+ * min_cross_distances_list and never fills it; evaluation.pose_checks_batch, host definition evaluation.pose_checks), for n_poses poses of
+ * n_complexes complexes that share n_receptors receptors in one launch, one 256-thread workgroup per pose.  Pose p belongs to complex
+ * pose_cplx[p] and has its N = cplx_n[c] heavy atoms at pos[pose_ptr[p] ..][3] and their van der Waals radii at lig_radius[pose_ptr[p] ..]
+ * (pose_ptr [n_poses + 1]: prefix sums in atoms).  Complex c is checked against receptor cplx_rec[c] (-1: none), whose A atoms are
+ * rec[rec_ptr[r] ..][4] = (x, y, z, radius) in the frame of the poses (rec_ptr [n_receptors + 1] in atoms; rec_dev aligned to 16 bytes),
+ * and, with cplx_tab[c] = 1, against its own tables at entry tab_ptr[c] of bounds / kind (tab_ptr [n_complexes + 1]: prefix sums of N * N
+ * ROUNDED UP TO A MULTIPLE OF FOUR for a complex with tables, 0 for one without): bounds [N][N] fp32 holds the upper bound of the pair at
+ * [i][j], i < j, and the lower at [j][i] (rdkit's layout); kind [N][N] bytes: 1 a bond, 2 a 1-3 pair, 0 any other pair; only i < j is read.
+ * With d = |x_i - x_j| in fp64 on the fp32 coordinates, over the pairs i < j:
+ *   kind 1: n_bad_bond counts d < (1 - bond_tol) lower or d > (1 + bond_tol) upper; bond_lo = min d / lower, bond_hi = max d / upper;
+ *   kind 2: n_bad_angle, angle_lo, angle_hi, the same with angle_tol;
+ *   kind 0: n_internal_clash counts d < (1 - clash_tol) lower; clash_ratio = min d / lower;
+ * and over all N x A pairs with ratio = d / (r_i + r_a): n_rec_clash counts ratio < rec_scale; rec_ratio = min ratio, attained at
+ * (rec_lig_atom, rec_atom) -- ties to the smaller ligand atom, then the smaller receptor atom; rec_dist = min d.  A category without pairs:
+ * count 0, +inf for a minimum, -inf for a maximum.  Every float is fp64 on the fp32 inputs, rounded to fp32 once.
+ * out [14][n_poses] 4-byte words, rows: bond_lo, bond_hi, angle_lo, angle_hi, clash_ratio, rec_ratio, rec_dist (fp32), n_bad_bond,
+ * n_bad_angle, n_internal_clash, n_rec_clash, rec_lig_atom, rec_atom, flags (int32).  flags: 1 bad bond, 2 bad angle, 4 internal clash,
+ * 8 receptor clash, 16 no tables (internal rows NaN / -1), 32 no receptor or one of 0 atoms (receptor rows NaN / -1), 64 a coordinate of the
+ * pose or of its receptor that is not finite, 128 a malformed table entry among i < j (not finite, lower <= 0, upper < lower, kind > 2) or,
+ * where the receptor checks run, a radius that is not finite and positive; with 64 or 128 every row is NaN / -1 and bits 1 to 8 are clear.
+ * A pose whose description contradicts itself -- pose_cplx names no complex, N outside [1, max_n], a pose_ptr extent that differs from
+ * N or starts below 0, cplx_rec outside [-1, n_receptors), cplx_tab outside {0, 1}, a tab_ptr / rec_ptr extent that is negative or
+ * contradicts N, a NULL array that it needs -- gets NaN / -1 and flags = 64; the kernel indexes with none of these before it has checked
+ * it (the lengths of the ragged arrays themselves are the caller's).  tab_ptr / bounds / kind may be NULL when no complex has tables,
+ * rec_ptr / rec when there is no receptor.  max_n: the largest N of the launch; capacity N <= 256: a larger value returns
+ * CBD_ERR_CAPACITY and nothing is launched or written.  The thresholds: the three tolerances in [0, 1), rec_scale > 0, else CBD_ERR_ARG.
+ * Minima, maxima and integer counts only -- no atomics, no scratch memory, no float sums: bitwise repeatable, and a pose's result does not
+ * depend on what shares the launch.  n_poses = 0 returns 0 without a launch.  Device pointers; asynchronous on `stream`. */
+int cbd_pose_checks(int32_t n_poses, int32_t n_complexes, int32_t n_receptors, int32_t max_n, const int32_t* pose_cplx_dev,
+                    const int32_t* pose_ptr_dev, const float* pos_dev, const float* lig_radius_dev, const int32_t* cplx_n_dev,
+                    const int32_t* cplx_rec_dev, const int32_t* cplx_tab_dev, const int32_t* tab_ptr_dev, const float* bounds_dev,
+                    const uint8_t* kind_dev, const int32_t* rec_ptr_dev, const float* rec_dev, float bond_tol, float angle_tol, float clash_tol,
+                    float rec_scale, int32_t* out_dev, void* stream);
+
 /* Ligand conformers by distance geometry (the first half of the reference's conformer matching: generate_conformer,
  * datasets/process_mols.py:591-607, rdkit's ETKDG there; here plain distance geometry along rdkit's useRandomCoords route, see
  * DESIGN.md section 9 and csrc/conformer_embed.hip).  n_conformers conformers of n_mols molecules in one launch, one workgroup of 4

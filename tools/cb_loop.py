@@ -3,7 +3,7 @@ defaults for the loop shape (README.md:52 of the reference: 8 samples per comple
 max_complexes_per_couple 20, EMA, 20 denoising steps) on a synthetic cluster of C2-sized complexes:
 
     python tools/cb_loop.py [--complexes 12] [--epochs 3] [--cb-inference-freq 1] [--device-noise] [--device-randomize]
-                            [--device-metrics] [--keep-distinct-rmsd A]
+                            [--device-metrics] [--keep-distinct-rmsd A] [--keep-valid]
 
 Prints per-epoch logs and one JSON line with the time split (sampling + confidence + RMSD / training) and the rates."""
 import argparse
@@ -23,11 +23,11 @@ sys.path.insert(0, ROOT)
 
 
 def run(complexes=12, epochs=3, cb_inference_freq=1, samples=8, steps=20, workload="c2_dockgen_median", host_threads=16, quiet=False,
-        device_noise=False, device_randomize=False, device_metrics=False, keep_distinct_rmsd=None):
+        device_noise=False, device_randomize=False, device_metrics=False, keep_distinct_rmsd=None, keep_valid=False):
     """-> dict with the time split of the loop (bench.py's `cb_round` leg calls this with the reference's loop shape)"""
     a = Namespace(complexes=complexes, epochs=epochs, cb_inference_freq=cb_inference_freq, samples=samples, steps=steps, workload=workload,
                   host_threads=host_threads, device_noise=device_noise, device_randomize=device_randomize,
-                  device_metrics=device_metrics, keep_distinct_rmsd=keep_distinct_rmsd)
+                  device_metrics=device_metrics, keep_distinct_rmsd=keep_distinct_rmsd, keep_valid=keep_valid)
     threads_before = torch.get_num_threads()
     torch.set_num_threads(a.host_threads)
     try:
@@ -71,7 +71,8 @@ def _run(a, quiet):
                          device_noise=a.device_noise,     # noise each training batch with one launch (NoiseTransform.apply_noise_batch)
                          device_randomize=a.device_randomize,     # starting poses of each group of complexes with one launch (randomize_position_batch)
                          device_metrics=a.device_metrics,     # RMSDs of each group of complexes with one launch and cached isomorphisms (pose_metrics_batch)
-                         keep_distinct_rmsd=a.keep_distinct_rmsd)     # keep only the heads of each complex's binding modes (cluster_poses_batch)
+                         keep_distinct_rmsd=a.keep_distinct_rmsd,     # keep only the heads of each complex's binding modes (cluster_poses_batch)
+                         keep_valid=a.keep_valid)     # keep only the poses that pass the distance checks (pose_checks_batch)
     t2s = partial(t_to_sigma, args=margs)
     buf = CBBuffer(cluster_name="c", cluster_to_ligands={"c": names}, max_complexes_per_couple=20,
                    transform=NoiseTransform(t_to_sigma=t2s, no_torsion=False, all_atom=False))
@@ -139,10 +140,12 @@ def main():
                     "with cached graph isomorphisms (off by default)")
     ap.add_argument("--keep-distinct-rmsd", type=float, default=None, help="of each complex's poses above the confidence cutoff, push only "
                     "the heads of its binding modes into the buffer: RMSD cutoff in Angstrom (default: none, every pose is kept)")
+    ap.add_argument("--keep-valid", action="store_true", help="push only the poses that pass the bond, 1-3, internal-clash and receptor-clash "
+                    "checks into the buffer (off by default)")
     a = ap.parse_args()
     print(json.dumps(run(a.complexes, a.epochs, a.cb_inference_freq, a.samples, a.steps, a.workload, a.host_threads,
                          device_noise=a.device_noise, device_randomize=a.device_randomize, device_metrics=a.device_metrics,
-                         keep_distinct_rmsd=a.keep_distinct_rmsd)))
+                         keep_distinct_rmsd=a.keep_distinct_rmsd, keep_valid=a.keep_valid)))
 
 
 if __name__ == "__main__":

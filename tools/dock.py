@@ -5,6 +5,7 @@
                                    | --protein-ligand-csv FILE)
                        [--samples 10] [--steps 20] [--lm-embeddings E.npy] [--score-model-dir D --ckpt F]
                        [--confidence-model-dir D --confidence-ckpt F] [--save-visualisation] [--seed 0] [--cluster-rmsd A]
+                       [--check-poses]
 
 Three ways to name the input:
   --ligand FILE               the conformer is SEEDED FROM THE FILE's coordinates (get_complex): bond lengths and angles of the given
@@ -23,6 +24,11 @@ randomised pose and the pose after every reverse-diffusion step as MODEL frames)
 --cluster-rmsd A (default: none) groups the poses of each complex into distinct binding modes: symmetry-corrected heavy-atom RMSD in the
 receptor frame, leader clustering in rank order with cutoff A (docking.ranked_modes: one GPU call per sampling() call), and adds
 mode{m}_rank{k}_confidence{c:.2f}.sdf per mode and modes.csv (mode, head_rank, population, best_confidence, mean_confidence).
+
+--check-poses (default: off) asks of every pose whether it is physically possible: bond lengths, 1-3 distances, internal clashes and
+clashes with the protein's heavy atoms (evaluation.pose_checks; docking.pose_check_rows: one GPU launch per sampling() call), written as
+pose_checks.csv next to the ranked SDFs, one row per rank.  Heavy atoms only; no volume-overlap, planarity, chirality or energy checks;
+waters and cofactors are not part of the receptor.  File names and ranking do not change.
 
 A model directory holds model_parameters.yml and the checkpoint.  Without one the model of the shipped architecture is built with
 random weights from --seed: the poses are then meaningless, which is good for a smoke run only.  --lm-embeddings: an .npy of shape
@@ -91,7 +97,7 @@ def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, de
     from confidence_bootstrapping_amd.sampling import sampling, randomize_position
     from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
     from confidence_bootstrapping_amd.visualise import PDBFile
-    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes
+    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes, pose_check_rows, write_pose_checks
     remove_hs = bool(getattr(margs, "remove_hs", True))
     with tempfile.TemporaryDirectory() as tmp:
         proteins = [_gunzip(p, tmp, k) for k, p in enumerate(proteins)]
@@ -150,6 +156,9 @@ def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, de
         modes = [None] * len(group)
         if a.cluster_rmsd is not None:      # the poses of all complexes of this sampling() call in one launch
             modes = ranked_modes([(cplx.mol, data_list[sl], confidence[sl]) for (_, cplx), sl in zip(group, slices)], dev, a.cluster_rmsd)
+        checks = [None] * len(group)
+        if a.check_poses:      # likewise one launch
+            checks = pose_check_rows([(cplx.mol, data_list[sl], confidence[sl], cplx) for (_, cplx), sl in zip(group, slices)], dev)
         for g, (idx, cplx) in enumerate(group):
             sl = slices[g]
             order = write_ranked_poses(out_dirs[idx], cplx.mol, data_list[sl], confidence[sl],
@@ -160,6 +169,10 @@ def _dock_descriptions(a, names, proteins, descriptions, sequences, out_dirs, de
                 print(f"  rank {rank + 1}: pose {i:2d}  confidence {conf[i]:+.4f}")
             if modes[g] is not None:
                 print(f"  {int(modes[g][1].max()) + 1} distinct binding modes at {a.cluster_rmsd} A")
+            if checks[g] is not None:
+                write_pose_checks(out_dirs[idx], checks[g])
+                valid = checks[g][2].valid
+                print(f"  pose checks: {int(valid.sum())} of {len(valid)} poses valid; rank 1 is {'valid' if valid[0] else 'NOT valid'}")
             results.append((names[idx], order, data_list[sl], confidence[sl]))
     return results
 
@@ -185,6 +198,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cluster-rmsd", type=float, default=None, help="group the poses into distinct binding modes with this RMSD cutoff in "
                     "Angstrom: adds mode*.sdf and modes.csv (default: none)")
+    ap.add_argument("--check-poses", action="store_true", help="check bond lengths, 1-3 distances, internal and receptor clashes of every pose: "
+                    "adds pose_checks.csv (default: off)")
     a = ap.parse_args(argv)
     if a.ligand is not None and not a.ligand.endswith((".sdf", ".mol2")):
         ap.error("the ligand must be an .sdf or .mol2 file")
@@ -194,7 +209,7 @@ def main(argv=None):
     from confidence_bootstrapping_amd.sampling import sampling, randomize_position
     from confidence_bootstrapping_amd.diffusion_utils import get_t_schedule, t_to_sigma
     from confidence_bootstrapping_amd.visualise import PDBFile
-    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes
+    from confidence_bootstrapping_amd.docking import write_ranked_poses, ranked_modes, pose_check_rows, write_pose_checks
     if not torch.cuda.is_available():
         raise RuntimeError("docking runs on the GPU: there is no CPU path")
     dev = torch.device("cuda:0")
@@ -260,6 +275,10 @@ def main(argv=None):
         print(f"  rank {rank + 1}: pose {i:2d}  confidence {conf[i]:+.4f}")
     if modes is not None:
         print(f"  {int(modes[1].max()) + 1} distinct binding modes at {a.cluster_rmsd} A")
+    if a.check_poses:
+        checks = pose_check_rows([(lig, data_list, confidence, cplx)], dev)[0]
+        write_pose_checks(a.out, checks)
+        print(f"  pose checks: {int(checks[2].valid.sum())} of {len(data_list)} poses valid; rank 1 is {'valid' if checks[2].valid[0] else 'NOT valid'}")
     return order, data_list, confidence
 
 
